@@ -37,6 +37,9 @@ Rank 0 prints ONE JSON line.  Besides the driver's contract it carries
 Every run checks parity: N = 1 against the CPU sample, N > 1 every rank's first and last 4 096 units
 against the oracle (MSM: the sum over ALL terms of all ranks against the closed form of structured
 points) - a mismatch anywhere makes the run exit non-zero.
+
+--dump-outputs DIR writes what the last timed step handed back (dump_outputs) after the timed region; the inputs come from
+fixed seeds, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -126,6 +129,45 @@ ECDSA_CORRUPT_EVERY = 7     # every 7th signature of the synthetic ECDSA batch h
 CHECK_LEN = 4096            # N > 1: units at each end of a rank's slice compared with the oracle
 MSM_A0 = 0x1234567890ABCDEF1234567890ABCDEF0F1E2D3C4B5A6978          # structured MSM points P_i = (A0 + i * D) G
 MSM_D = 0xFEDCBA0987654321
+DUMP_ROWS = 1 << 17         # --dump-outputs: units kept of an element-wise output (p384: 2^17 x 26 float64 = 27 MB, under the 64 MB cap)
+DUMP_SEED = 0xD0E5
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# --dump-outputs: what the timed path handed back in its last step, so that two builds can be compared output for output
+# ---------------------------------------------------------------------------------------------------------------------
+def dump_rows(n):
+    """Units written for an element-wise output of n units: all of them up to DUMP_ROWS, else a fixed seeded sample (sorted)."""
+    import numpy as np
+    if n <= DUMP_ROWS:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_ROWS, replace=False))
+
+
+def dump_outputs(path, wl, n, d_o, d_i):
+    """Write the outputs of one step as float64 .npy files under `path`.  Coordinates are stored as their big-endian 32-bit
+    words (exact in float64): xy.npy is (units, 2 * field bytes / 4); infinity.npy (point results) and valid.npy (ECDSA
+    verification) are the 0 / 1 flags; index.npy names the units kept.  The MSM's one affine point is written whole."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+
+    def words(t):
+        return np.ascontiguousarray(t.cpu().numpy()).view(">u4").astype(np.float64)
+
+    if wl["msm"]:
+        arrays = {"xy": words(d_o)}
+    else:
+        idx = dump_rows(n)
+        sel = torch.from_numpy(idx).to(d_i.device)
+        arrays = {"index": idx.astype(np.float64)}
+        if wl.get("ecdsa"):
+            arrays["valid"] = d_i[sel].cpu().numpy().astype(np.float64)
+        else:
+            arrays["xy"] = words(d_o[sel])
+            arrays["infinity"] = d_i[sel].cpu().numpy().astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -344,8 +386,9 @@ def pmc_summary(workload, log2n, default_size):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-def run_workload(env, name, log2n, steps, warmup, schedule, cpu):
-    """Generate inputs on the device, time `steps` passes, check parity.  env: torch, ecgpu, ctx, dev, rank, world, dist, backend."""
+def run_workload(env, name, log2n, steps, warmup, schedule, cpu, dump=None):
+    """Generate inputs on the device, time `steps` passes, check parity.  env: torch, ecgpu, ctx, dev, rank, world, dist, backend.
+    dump: directory for the outputs of the last timed step (rank 0's; dump_outputs)."""
     import numpy as np
     torch, ecgpu, ctx, dev = env["torch"], env["ecgpu"], env["ctx"], env["dev"]
     rank, world, dist, backend = env["rank"], env["world"], env["dist"], env["backend"]
@@ -441,6 +484,8 @@ def run_workload(env, name, log2n, steps, warmup, schedule, cpu):
         t = torch.tensor([elapsed], dtype=torch.float64, device=(dev if backend == "nccl" else "cpu"))
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if dump and rank == 0:
+        dump_outputs(dump, wl, n, d_o, d_i)
 
     # ---- parity ---------------------------------------------------------------------------------------------------------
     parity, checked = True, []
@@ -734,7 +779,14 @@ def main():
     ap.add_argument("--inproc", action="store_true",
                     help="drive all --gpus N devices from THIS process through the library's device group (ecgpu_group_*) instead of one process per GPU")
     ap.add_argument("--same-device", action="store_true", help="--inproc: put all group members on device 0 (rehearsal on a one-GPU box)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (rank 0's slice) as DIR/<name>.npy, float64: "
+                         "a fixed seeded sample of %d units of an element-wise output, the MSM's point whole" % DUMP_ROWS)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.inproc and args.dump_outputs:
+        ap.error("--dump-outputs is not available with --inproc")
     if args.inproc:
         return run_inproc(args)
     maybe_launch_ranks(args)
@@ -803,7 +855,7 @@ def main():
            "backend": args.backend, "host_io": (world == 1 and rank == 0 and not args.no_host_io and args.log2n >= 21)}
 
     with torch.cuda.stream(stream):
-        res = run_workload(env, args.workload, args.log2n, args.steps, args.warmup, args.schedule, cpu)
+        res = run_workload(env, args.workload, args.log2n, args.steps, args.warmup, args.schedule, cpu, dump=args.dump_outputs)
         other_res = []
         for o in others:
             other_res.append(run_workload(env, o, WORKLOADS[o]["log2n"], max(2, min(args.steps, 5)), 1, "fast", cpu_others.get(o)))

@@ -24,7 +24,7 @@ un-vendored crates), so this is a restatement.  Two layers:
   integers mod p gives the same canonical (X, Y, Z) bytes as the reference's
   lazily-reduced 5x52 / Montgomery limbs after ``normalize`` / ``to_canonical``.
 
-All paths cited are relative to /root/reference.
+All paths cited are relative to the root of the reference checkout.
 """
 from __future__ import annotations
 

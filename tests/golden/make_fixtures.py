@@ -1,12 +1,13 @@
 #!/usr/bin/env python3
 """Scrape the reference's own known-answer vectors for the hot path into JSON fixtures.
 
-Run in the build container only (needs /root/reference, which never travels to the GPU box):
+Needs a checkout of the reference (RustCrypto elliptic-curves, risc0 fork); the tests read only the
+fixtures it writes:
 
-    python tests/golden/make_fixtures.py
+    python tests/golden/make_fixtures.py <path of the reference checkout>
 
 Only DATA is extracted (hex literals: inputs and expected outputs); no reference source text is
-kept.  Sources (relative to /root/reference), see SURVEY.md section 8c:
+kept.  Sources (relative to the reference checkout), see SURVEY.md section 8c:
 
   <curve>/src/test_vectors/group.rs     ADD_TEST_VECTORS (k*G for k = 1..20), MUL_TEST_VECTORS (k, x, y)
   <curve>/src/test_vectors/ecdsa.rs     d -> (q_x, q_y), k -> r   (fixed-base KATs)
@@ -26,7 +27,7 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
-REF = "/root/reference"
+REF = None            # the reference checkout (command line)
 sys.path.insert(0, ROOT)
 
 from oracle import ecmodel as M  # noqa: E402
@@ -234,4 +235,7 @@ def main():
 
 
 if __name__ == "__main__":
+    if len(sys.argv) != 2:
+        sys.exit("usage: python tests/golden/make_fixtures.py <path of the reference checkout>")
+    REF = sys.argv[1]
     main()

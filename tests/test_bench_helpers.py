@@ -40,3 +40,33 @@ def test_spread_blocks_end_at_the_batch_end():
     st = bench.spread_blocks(n, sample)
     assert len(st) == bench.SPREAD_BLOCKS and st[0] == sample and st[-1] + bench.SPREAD_LEN == n
     assert bench.spread_blocks(4096, 4096) == []
+
+
+def test_dump_outputs_sample_and_encoding(tmp_path):
+    """--dump-outputs: a fixed seeded sample of units, coordinates as exact big-endian 32-bit words in float64, under 64 MB."""
+    import torch
+    n = 2 * bench.DUMP_ROWS
+    rng = np.random.default_rng(1)
+    for name in ("k256_varbase", "p384_varbase", "k256_ecdsa_verify"):
+        wl = bench.WORKLOADS[name]
+        nb = 48 if wl["curve"] == "p384" else 32
+        d_o = torch.from_numpy(rng.integers(0, 256, (n, 2 * nb), dtype=np.uint8))
+        d_i = torch.from_numpy(rng.integers(0, 2, n, dtype=np.uint8))
+        bench.dump_outputs(str(tmp_path / name), wl, n, d_o, d_i)
+        files = {f.stem: np.load(f) for f in (tmp_path / name).iterdir()}
+        assert all(a.dtype == np.float64 for a in files.values())
+        assert sum(f.stat().st_size for f in (tmp_path / name).iterdir()) <= 64 << 20
+        idx = files["index"].astype(np.int64)
+        assert len(idx) == bench.DUMP_ROWS and (np.diff(idx) > 0).all() and idx[-1] < n
+        assert (idx == bench.dump_rows(n)).all()
+        if wl.get("ecdsa"):
+            assert set(files) == {"index", "valid"} and (files["valid"] == d_i.numpy()[idx]).all()
+        else:
+            assert set(files) == {"index", "xy", "infinity"} and (files["infinity"] == d_i.numpy()[idx]).all()
+            xy = files["xy"].astype(">u4").view(np.uint8).reshape(len(idx), 2 * nb)
+            assert (xy == d_o.numpy()[idx]).all()
+    assert (bench.dump_rows(1000) == np.arange(1000)).all()
+    d_o = torch.from_numpy(rng.integers(0, 256, (1, 64), dtype=np.uint8))
+    bench.dump_outputs(str(tmp_path / "msm"), bench.WORKLOADS["k256_msm"], n, d_o, torch.zeros(n, dtype=torch.uint8))
+    xy = np.load(tmp_path / "msm" / "xy.npy")
+    assert xy.shape == (1, 16) and (xy.astype(">u4").view(np.uint8).reshape(1, 64) == d_o.numpy()).all()
