@@ -158,6 +158,87 @@ ECGPU_HD void mul_add2(FeK256& r, const FeK256& a, const FeK256& b, const FeK256
   fold_top_fast(r.v, T);
 }
 
+// Column K of s^2 with the cross products already doubled: s^2 = sum_i s_i^2 B^2i + sum_{i <= 6} s_i B^i T_i, B = 2^32, where
+// T_i = 2 sum_{j > i} s_j B^j has the words e_(i+1) = s_(i+1) << 1 at B^(i+1) and d_j = (s_j << 1) | (s_(j-1) >> 31) at B^j for
+// i + 2 <= j <= 8 (d_8 = s_7 >> 31, the bit shifted out of the top).  35 doubled cross products and 8 squares: 43 multiply-accumulate
+// pairs on the columns instead of the 64 of a general product, and no separate doubling pass.
+constexpr int sqr2_terms(int K) {
+  int m = 0;
+  if (K % 2 == 1 && (K - 1) / 2 <= 6) m++;                 // s_i e_(i+1)
+  if (K % 2 == 0 && K / 2 <= 7) m++;                       // s_i^2
+  for (int i = 0; i <= 6; i++)
+    if (K - i >= i + 2 && K - i <= 8) m++;                 // s_i d_j
+  return m;
+}
+template <int K>
+ECGPU_HD void sqr2_column_terms(u32* pa, u32* pb, const u32* s, const u32* e, const u32* d) {
+  int m = 0;
+  if constexpr (K % 2 == 1 && (K - 1) / 2 <= 6) { pa[m] = s[(K - 1) / 2]; pb[m] = e[(K + 1) / 2]; m++; }
+  if constexpr (K % 2 == 0 && K / 2 <= 7) { pa[m] = s[K / 2]; pb[m] = s[K / 2]; m++; }
+#pragma unroll
+  for (int i = 0; i <= 6; i++)
+    if (K - i >= i + 2 && K - i <= 8) { pa[m] = s[i]; pb[m] = d[K - i]; m++; }
+}
+// e[1..7] and d[2..8] of the layout above (e[0], d[0], d[1] unused)
+ECGPU_HD void sqr2_operands(u32* e, u32* d, const u32* s) {
+#pragma unroll
+  for (int j = 1; j < 8; j++) e[j] = s[j] << 1;
+#pragma unroll
+  for (int j = 2; j < 8; j++) d[j] = (s[j] << 1) | (s[j - 1] >> 31);
+  d[8] = s[7] >> 31;
+}
+// column K of a * b + s^2, plus NX extra products (the fold terms of the low half)
+template <int K, int NX, bool FRESH>
+ECGPU_HD void mulsq_column(Acc96& c, const u32* a, const u32* b, const u32* s, const u32* e, const u32* d, const u32* xa, const u32* xb) {
+  constexpr int LO = (K - 7) > 0 ? (K - 7) : 0;
+  constexpr int HI = K < 7 ? K : 7;
+  constexpr int M = HI - LO + 1;
+  constexpr int MS = sqr2_terms(K);
+  u32 pa[M + MS + NX + 1], pb[M + MS + NX + 1];
+#pragma unroll
+  for (int m = 0; m < M; m++) { pa[m] = a[LO + m]; pb[m] = b[K - LO - m]; }
+  sqr2_column_terms<K>(pa + M, pb + M, s, e, d);
+#pragma unroll
+  for (int m = 0; m < NX; m++) { pa[M + MS + m] = xa[m]; pb[M + MS + m] = xb[m]; }
+  mac_cols<M + MS + NX, FRESH>(c, pa, pb);
+}
+template <int K>
+ECGPU_HD void mulsq_high_column(u32* h, Acc96& c, const u32* a, const u32* b, const u32* s, const u32* e, const u32* d) {
+  mulsq_column<K, 0, true>(c, a, b, s, e, d, nullptr, nullptr);
+  h[K - 8] = acc_pop(c);
+}
+template <int K>
+ECGPU_HD void mulsq_low_column(u32* t, Acc96& c, const u32* a, const u32* b, const u32* s, const u32* e, const u32* d, const u32* h) {
+  const u32 xa[1] = {h[K]}, xb[1] = {C_LO};
+  mulsq_column<K, 1, true>(c, a, b, s, e, d, xa, xb);
+  t[K] = acc_pop(c);
+}
+// r = a * b + s^2 mod p (weakly reduced): mul_add2 with a square as its second product (the doubling's Y3).  The sum is < 2^513, so
+// word 16 is handled as in mul_add2.
+ECGPU_HD void mul_add_sqr(FeK256& r, const FeK256& a, const FeK256& b, const FeK256& s) {
+  u32 e[8], d[9], h[8], t[8];
+  e[0] = 0; d[0] = 0; d[1] = 0;
+  sqr2_operands(e, d, s.v);
+  Acc96 c{0, 0};
+  mulsq_high_column<8>(h, c, a.v, b.v, s.v, e, d);  mulsq_high_column<9>(h, c, a.v, b.v, s.v, e, d);
+  mulsq_high_column<10>(h, c, a.v, b.v, s.v, e, d); mulsq_high_column<11>(h, c, a.v, b.v, s.v, e, d);
+  mulsq_high_column<12>(h, c, a.v, b.v, s.v, e, d); mulsq_high_column<13>(h, c, a.v, b.v, s.v, e, d);
+  mulsq_high_column<14>(h, c, a.v, b.v, s.v, e, d);
+  h[7] = (u32)c.lo;
+  const u32 h8 = (u32)(c.lo >> 32);                 // word 16 of the sum: 0 or 1
+  c.lo = 0; c.hi = 0;
+  mulsq_low_column<0>(t, c, a.v, b.v, s.v, e, d, h); mulsq_low_column<1>(t, c, a.v, b.v, s.v, e, d, h);
+  mulsq_low_column<2>(t, c, a.v, b.v, s.v, e, d, h); mulsq_low_column<3>(t, c, a.v, b.v, s.v, e, d, h);
+  mulsq_low_column<4>(t, c, a.v, b.v, s.v, e, d, h); mulsq_low_column<5>(t, c, a.v, b.v, s.v, e, d, h);
+  mulsq_low_column<6>(t, c, a.v, b.v, s.v, e, d, h); mulsq_low_column<7>(t, c, a.v, b.v, s.v, e, d, h);
+  u32 cy = 0;
+  r.v[0] = t[0];
+#pragma unroll
+  for (int i = 1; i < 8; i++) r.v[i] = addc(t[i], h[i - 1], cy);
+  const u64 T = c.lo + h[7] + cy + (((u64)h8 << 32) | (h8 ? C_LO : 0u));     // < 2^38
+  fold_top_fast(r.v, T);
+}
+
 // reduce a 16-word integer modulo p: lo + hi * 977 + (hi << 32), then fold what spills over 2^256
 ECGPU_HD void reduce16(FeK256& r, const u32* w) {
   u32 u[8];
@@ -216,6 +297,37 @@ ECGPU_HD void sub(FeK256& r, const FeK256& a, const FeK256& b) {
     r.v[0] = subb(r.v[0], b2 ? C_LO : 0u, b3);
     r.v[1] = subb(r.v[1], b2, b3);
   }
+}
+
+// r = a - b - c mod p: two borrow chains and ONE fold of the combined borrow w in {0, 1, 2} (a - b - c + w 2^256 is the 8-word
+// value, and 2^256 = C mod p), instead of two subtractions with a fold each.
+ECGPU_HD void sub2(FeK256& r, const FeK256& a, const FeK256& b, const FeK256& c) {
+  const u32 w = mp_sub<8>(r.v, a.v, b.v) + mp_sub<8>(r.v, r.v, c.v);
+  u32 b2 = 0;
+  r.v[0] = subb(r.v[0], w * C_LO, b2);
+  r.v[1] = subb(r.v[1], w, b2);
+  if (ECGPU_K256_RARE(b2 != 0)) {
+#pragma unroll
+    for (int i = 2; i < 8; i++) r.v[i] = subb(r.v[i], 0u, b2);
+    // wrapped below 0 once more: the value is now within 2C of 2^256, one more fold cannot borrow past word 1
+    u32 b3 = 0;
+    r.v[0] = subb(r.v[0], b2 ? C_LO : 0u, b3);
+    r.v[1] = subb(r.v[1], b2, b3);
+  }
+}
+
+// r = a / 2 mod p: (a + p) / 2 for an odd a, a / 2 for an even one.  a + p < 2^257, so the halved value is below 2^256 (weakly
+// reduced) and no fold is needed: one masked carry chain and a funnel shift, no branch.  r may alias a.
+ECGPU_HD void half(FeK256& r, const FeK256& a) {
+  const u32 m = 0u - (a.v[0] & 1u);
+  u32 t[8], c = 0;
+  t[0] = addc(a.v[0], m & (0u - C_LO), c);       // p = 2^256 - 2^32 - 977: words 0xFFFFFC2F, 0xFFFFFFFE, then all ones
+  t[1] = addc(a.v[1], m & 0xFFFFFFFEu, c);
+#pragma unroll
+  for (int i = 2; i < 8; i++) t[i] = addc(a.v[i], m, c);
+#pragma unroll
+  for (int i = 0; i < 7; i++) r.v[i] = (t[i] >> 1) | (t[i + 1] << 31);
+  r.v[7] = (t[7] >> 1) | (c << 31);
 }
 
 ECGPU_HD void set_zero(FeK256& r) { mp_zero<8>(r.v); }

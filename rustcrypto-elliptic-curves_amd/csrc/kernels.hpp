@@ -319,17 +319,19 @@ __device__ __forceinline__ void k256_fast_loop(JacK256* out, const K256FastPrep*
   const bool n1 = pp->neg1 != 0, n2 = pp->neg2 != 0;
   JacK256 acc;
   k256::set_zero(acc.x); k256::set_zero(acc.y); k256::set_zero(acc.z);      // infinity
+  bool flip = false;                     // the point is (-1)^flip acc: the doublings and additions below return negated results
   // the top position (WB = 4: the carry digits) then the others; one shared body for all positions
 #pragma unroll 1
   for (int i = NPOS - 1; i >= 0; i--) {
     if (i != NPOS - 1) {
 #pragma unroll 1
-      for (int j = 0; j < WB; j++) k256::jac_double(acc);
+      for (int j = 0; j < WB; j++) { k256::jac_double_neg(acc); flip = !flip; }
     }
     const int dg1 = k256::half_digit<WB>(w1, i), dg2 = k256::half_digit<WB>(w2, i);
 #pragma unroll 1
-    for (int h = 0; h < 2; h++) k256::add_digit(acc, tab, h ? dg2 : dg1, h != 0, h ? n2 : n1);
+    for (int h = 0; h < 2; h++) k256::add_digit_neg(acc, flip, tab, h ? dg2 : dg1, h != 0, h ? n2 : n1);
   }
+  if (flip) k256::neg(acc.y, acc.y);
   k256::mul(acc.z, acc.z, pp->zfix);     // back from the isomorphic curves
   if (pp->p_inf) k256::set_zero(acc.z);
   *out = acc;

@@ -85,6 +85,25 @@ ECGPU_HD void jac_double(JacK256& p) {
 }
 ECGPU_HD void jac_double(JacK256& r, const JacK256& p) { r = p; jac_double(r); }
 
+// In-place p <- -2p (a = 0) for the throughput loop, which keeps the sign of its accumulator aside (k256_fast_loop, mul_fast_jac).
+// The doubling above rescaled by u = 1/2 ((X, Y, Z) ~ (X/4, Y/8, Z/2)) with Y negated: S = Y^2, L = 3 X^2 / 2, T = X S,
+//   X3 = L^2 - 2T,  -Y3 = L (X3 - T) + S^2,  Z3 = Y Z
+// (the form libsecp256k1's secp256k1_gej_double uses).  One halving replaces the scalings 2 Y Z, 4 X B, 3 A and -8 B of jac_double,
+// the negation is free, and S^2 rides on the columns of L (X3 - T) as a square (43 products, not 64).  Same 4M + 3S count; infinity
+// (Z = 0) stays infinity.
+ECGPU_HD void jac_double_neg(JacK256& p) {
+  FeK256 s, l, t;
+  sqr(s, p.y);                               // S
+  mul(p.z, p.y, p.z);                        // Z3
+  sqr(l, p.x);                               // A = X^2
+  mul(t, p.x, s);                            // T
+  half(p.y, l); add(l, l, p.y);              // L = A + A/2
+  sqr(p.y, l);
+  sub2(p.x, p.y, t, t);                      // X3 = L^2 - 2T
+  sub(t, p.x, t);                            // X3 - T
+  mul_add_sqr(p.y, l, t, s);                 // -Y3 = L (X3 - T) + S^2
+}
+
 // doubling of an affine point (Z = 1)
 ECGPU_HD void jac_double_affine(JacK256& r, const FeK256& x, const FeK256& y) {
   r.x = x; r.y = y; set_one(r.z);
@@ -134,6 +153,35 @@ ECGPU_HD void jac_add_mixed(JacK256& p, const FeK256& x2, const FeK256& y2, FeK2
 ECGPU_HD void jac_add_mixed(JacK256& r, const JacK256& p, const FeK256& x2, const FeK256& y2, FeK256* zr) {
   r = p;
   jac_add_mixed(r, x2, y2, zr);
+}
+
+// In-place p <- -(p + (x2, y2)) for the throughput loop (see jac_double_neg): the formula of jac_add_mixed with Y3 negated,
+// -Y3 = R (X3 - V) + Y1 HHH, which needs no negation of Y1, and X3 = R^2 - HHH - 2V with one fold for both subtractions of 2V.
+// The exceptional cases (p at infinity, p = (x2, y2)) take the exact paths of jac_add_mixed and negate the result.
+ECGPU_HD void jac_add_mixed_neg(JacK256& p, const FeK256& x2, const FeK256& y2) {
+  if (is_zero_fast(p.z)) {
+    p.x = x2; neg(p.y, y2); set_one(p.z);
+    return;
+  }
+  FeK256 h, r, t, u;
+  sqr(t, p.z);                               // Z1Z1
+  mul(h, x2, t);                             // U2
+  mul(t, p.z, t); mul(r, t, y2);             // S2
+  sub(h, h, p.x);                            // H
+  sub(r, r, p.y);                            // R
+  if (__builtin_expect(is_zero_fast(h) && is_zero(r), 0)) {   // never taken for honest GLV digits; kept exact
+    jac_double_affine(p, x2, y2);
+    neg(p.y, p.y);
+    return;
+  }
+  mul(p.z, p.z, h);                          // Z3
+  sqr(t, h);                                 // HH
+  mul(h, t, h);                              // HHH
+  mul(t, p.x, t);                            // V
+  sqr(u, r);
+  sub(u, u, h); sub2(p.x, u, t, t);          // X3 = R^2 - HHH - 2V
+  sub(t, p.x, t);                            // X3 - V
+  mul_add2(p.y, r, t, p.y, h);               // -Y3 = R (X3 - V) + Y1 HHH
 }
 
 // Doubling of an affine point with update (co-Z, a = 0; 2M + 4S): d = 2P in Jacobian coordinates with Z = 2y, and
@@ -272,6 +320,29 @@ ECGPU_HD void add_digit(JacK256& acc, const TabSlotK256* tab, int d, bool lam, b
   }
 }
 
+// add_digit for the accumulator of the throughput loop, which holds the point (-1)^flip acc: the table point goes in negated once
+// more when flip is set, jac_add_mixed_neg returns the negated sum, and a non-zero digit therefore toggles flip.
+ECGPU_HD void add_digit_neg(JacK256& acc, bool& flip, const TabSlotK256* tab, int d, bool lam, bool neg) {
+  const int ad = d < 0 ? -d : d;
+  if (ad != 0) {
+#ifdef ECGPU_K256_NO_BETA_SLOTS
+    const TabSlotK256* e = tab + (ad - 1);
+    ECGPU_TABLE_TOUCH(ad - 1);
+    FeK256 x = e->x;
+    FeK256 y = e->y;
+    if (lam) { FeK256 b; beta(b); mul(x, x, b); }
+#else
+    const TabSlotK256* e = tab + (2 * (ad - 1) + (lam ? 1 : 0));
+    ECGPU_TABLE_TOUCH(2 * (ad - 1) + (lam ? 1 : 0));
+    FeK256 x = e->x;
+    FeK256 y = e->y;
+#endif
+    if ((neg != (d < 0)) != flip) k256::neg(y, y);
+    jac_add_mixed_neg(acc, x, y);
+    flip = !flip;
+  }
+}
+
 // k * P for an affine, non-identity P; result in Jacobian coordinates on secp256k1.
 template <int WB>
 ECGPU_HD void mul_fast_jac(JacK256& acc, const FeK256& px, const FeK256& py, const u32* k, TabSlotK256* tab) {
@@ -284,15 +355,17 @@ ECGPU_HD void mul_fast_jac(JacK256& acc, const FeK256& px, const FeK256& py, con
   recode_half<WB>(w1, s.k1);
   recode_half<WB>(w2, s.k2);
   set_zero(acc.x); set_zero(acc.y); set_zero(acc.z);      // infinity
+  bool flip = false;                                      // the point is (-1)^flip acc
 #pragma unroll 1
   for (int i = NPOS - 1; i >= 0; i--) {
     if (i != NPOS - 1) {
 #pragma unroll 1
-      for (int j = 0; j < WB; j++) jac_double(acc);
+      for (int j = 0; j < WB; j++) { jac_double_neg(acc); flip = !flip; }
     }
 #pragma unroll 1
-    for (int h = 0; h < 2; h++) add_digit(acc, tab, half_digit<WB>(h ? w2 : w1, i), h != 0, h ? s.neg2 : s.neg1);
+    for (int h = 0; h < 2; h++) add_digit_neg(acc, flip, tab, half_digit<WB>(h ? w2 : w1, i), h != 0, h ? s.neg2 : s.neg1);
   }
+  if (flip) neg(acc.y, acc.y);
   mul(acc.z, acc.z, zg);     // back from the isomorphic curve
 }
 
