@@ -86,15 +86,32 @@ ECGPU_HD void fold_top_fast(u32* r, u64 T) {
 // together with H*C, so the pseudo-Mersenne fold rides on the same 96-bit accumulator.
 // One asm statement per column (hipcc pads each asm statement with an s_nop): the column's
 // products, and for the low half also h[k]*977 and h[k-1]*1, go into a single statement.
+//
+// Products that cannot carry out of the accumulator's low 64 bits lead their column and go in without a carry addition
+// (mac_cols NC):
+//  - the fold product h[K] * 977 of low column K: the carry popped into a column is < 2^37 (every column of mul, mul_add2
+//    and mul_add_sqr sums at most 17 products below 2^64 and its own carry-in, < 2^69), h[K] * 977 < 2^42, their sum < 2^43;
+//  - the first product of high column 8, which starts from the zeroed accumulator;
+//  - in mul_add_sqr, s_i * d_8 (d_8 = s_7 >> 31 is 0 or 1, so the product is < 2^32) on a popped carry, and in column 8 the
+//    product after it: < 2^32 + (2^32 - 1)^2 < 2^64.
+namespace nc_bound {
+using u128 = unsigned __int128;
+constexpr u128 MAX_PRODUCT = (u128)0xFFFFFFFFu * 0xFFFFFFFFu;
+static_assert(17 * MAX_PRODUCT + ((u128)1 << 37) < ((u128)1 << 69), "a column with a carry-in < 2^37 sums to < 2^69: it pops < 2^37");
+static_assert(((u128)1 << 37) + (u128)0xFFFFFFFFu * C_LO < ((u128)1 << 43), "fold product on a popped carry: < 2^43, no carry");
+static_assert(((u128)1 << 37) + 0xFFFFFFFFu < ((u128)1 << 64), "s_i * d_8 on a popped carry: no carry");
+static_assert((u128)0xFFFFFFFFu + MAX_PRODUCT < ((u128)1 << 64), "s_0 * d_8 then one product on a zeroed accumulator: no carry");
+}  // namespace nc_bound
 template <int K>
 ECGPU_HD void mul_high_column(u32* h, Acc96& c, const u32* a, const u32* b) {
-  mac_product_column<8, K, 0, true>(c, a, b, nullptr, nullptr);     // c.hi == 0: fresh accumulator or just popped
+  // c.hi == 0: fresh accumulator or just popped.  Column 8 starts from zero: its first product cannot carry.
+  mac_product_column<8, K, 0, true, (K == 8 ? 1 : 0)>(c, a, b, nullptr, nullptr);
   h[K - 8] = acc_pop(c);
 }
 template <int K>
 ECGPU_HD void mul_low_column(u32* t, Acc96& c, const u32* a, const u32* b, const u32* h) {
   const u32 xa[1] = {h[K]}, xb[1] = {C_LO};
-  mac_product_column<8, K, 1, true>(c, a, b, xa, xb);
+  mac_product_column<8, K, 1, true, 1>(c, a, b, xa, xb);      // h[K] * 977 first: < 2^43 with the carry-in (nc_bound)
   t[K] = acc_pop(c);
 }
 ECGPU_HD void mul(FeK256& r, const FeK256& a, const FeK256& b) {
@@ -125,14 +142,15 @@ ECGPU_HD void mul(FeK256& r, const FeK256& a, const FeK256& b) {
 // 2^512 = C^2 mod p, i.e. it adds C to the overflow count T that fold_top_fast multiplies by C.
 template <int K>
 ECGPU_HD void mul2_high_column(u32* h, Acc96& c, const u32* a, const u32* b, const u32* e, const u32* f) {
-  mac_product_column<8, K, 0, true>(c, a, b, nullptr, nullptr);     // c.hi == 0: fresh accumulator or just popped
+  // c.hi == 0: fresh accumulator or just popped.  Column 8 starts from zero: its first product cannot carry.
+  mac_product_column<8, K, 0, true, (K == 8 ? 1 : 0)>(c, a, b, nullptr, nullptr);
   mac_product_column<8, K, 0, false>(c, e, f, nullptr, nullptr);
   h[K - 8] = acc_pop(c);
 }
 template <int K>
 ECGPU_HD void mul2_low_column(u32* t, Acc96& c, const u32* a, const u32* b, const u32* e, const u32* f, const u32* h) {
   const u32 xa[1] = {h[K]}, xb[1] = {C_LO};
-  mac_product_column<8, K, 1, true>(c, a, b, xa, xb);
+  mac_product_column<8, K, 1, true, 1>(c, a, b, xa, xb);      // h[K] * 977 first: < 2^43 with the carry-in (nc_bound)
   mac_product_column<8, K, 0, false>(c, e, f, nullptr, nullptr);
   t[K] = acc_pop(c);
 }
@@ -170,6 +188,8 @@ constexpr int sqr2_terms(int K) {
     if (K - i >= i + 2 && K - i <= 8) m++;                 // s_i d_j
   return m;
 }
+// the terms of column K except s_(K-8) d_8, which mulsq_column puts first (columns 8..14 have one)
+constexpr bool sqr2_has_d8(int K) { return K >= 8 && K <= 14; }
 template <int K>
 ECGPU_HD void sqr2_column_terms(u32* pa, u32* pb, const u32* s, const u32* e, const u32* d) {
   int m = 0;
@@ -177,7 +197,7 @@ ECGPU_HD void sqr2_column_terms(u32* pa, u32* pb, const u32* s, const u32* e, co
   if constexpr (K % 2 == 0 && K / 2 <= 7) { pa[m] = s[K / 2]; pb[m] = s[K / 2]; m++; }
 #pragma unroll
   for (int i = 0; i <= 6; i++)
-    if (K - i >= i + 2 && K - i <= 8) { pa[m] = s[i]; pb[m] = d[K - i]; m++; }
+    if (K - i >= i + 2 && K - i <= 7) { pa[m] = s[i]; pb[m] = d[K - i]; m++; }
 }
 // e[1..7] and d[2..8] of the layout above (e[0], d[0], d[1] unused)
 ECGPU_HD void sqr2_operands(u32* e, u32* d, const u32* s) {
@@ -187,30 +207,35 @@ ECGPU_HD void sqr2_operands(u32* e, u32* d, const u32* s) {
   for (int j = 2; j < 8; j++) d[j] = (s[j] << 1) | (s[j - 1] >> 31);
   d[8] = s[7] >> 31;
 }
-// column K of a * b + s^2, plus NX extra products (the fold terms of the low half)
-template <int K, int NX, bool FRESH>
+// column K of a * b + s^2, plus NX extra products (the fold terms of the low half).  Order: the extra products, s_(K-8) d_8,
+// the products of a * b, the other square terms; NC: the first NC of them cannot carry out of c.lo, as the caller states.
+template <int K, int NX, bool FRESH, int NC>
 ECGPU_HD void mulsq_column(Acc96& c, const u32* a, const u32* b, const u32* s, const u32* e, const u32* d, const u32* xa, const u32* xb) {
   constexpr int LO = (K - 7) > 0 ? (K - 7) : 0;
   constexpr int HI = K < 7 ? K : 7;
   constexpr int M = HI - LO + 1;
   constexpr int MS = sqr2_terms(K);
+  constexpr int D8 = sqr2_has_d8(K) ? 1 : 0;
   u32 pa[M + MS + NX + 1], pb[M + MS + NX + 1];
 #pragma unroll
-  for (int m = 0; m < M; m++) { pa[m] = a[LO + m]; pb[m] = b[K - LO - m]; }
-  sqr2_column_terms<K>(pa + M, pb + M, s, e, d);
+  for (int m = 0; m < NX; m++) { pa[m] = xa[m]; pb[m] = xb[m]; }
+  if constexpr (D8) { pa[NX] = s[K - 8]; pb[NX] = d[8]; }
 #pragma unroll
-  for (int m = 0; m < NX; m++) { pa[M + MS + m] = xa[m]; pb[M + MS + m] = xb[m]; }
-  mac_cols<M + MS + NX, FRESH>(c, pa, pb);
+  for (int m = 0; m < M; m++) { pa[NX + D8 + m] = a[LO + m]; pb[NX + D8 + m] = b[K - LO - m]; }
+  sqr2_column_terms<K>(pa + NX + D8 + M, pb + NX + D8 + M, s, e, d);
+  mac_cols<M + MS + NX, FRESH, NC>(c, pa, pb);
 }
 template <int K>
 ECGPU_HD void mulsq_high_column(u32* h, Acc96& c, const u32* a, const u32* b, const u32* s, const u32* e, const u32* d) {
-  mulsq_column<K, 0, true>(c, a, b, s, e, d, nullptr, nullptr);
+  // s_(K-8) d_8 < 2^32 first, on a popped carry; column 8 starts from zero and its next product cannot carry either (nc_bound)
+  static_assert(sqr2_has_d8(K), "every high column has its d_8 term");
+  mulsq_column<K, 0, true, (K == 8 ? 2 : 1)>(c, a, b, s, e, d, nullptr, nullptr);
   h[K - 8] = acc_pop(c);
 }
 template <int K>
 ECGPU_HD void mulsq_low_column(u32* t, Acc96& c, const u32* a, const u32* b, const u32* s, const u32* e, const u32* d, const u32* h) {
   const u32 xa[1] = {h[K]}, xb[1] = {C_LO};
-  mulsq_column<K, 1, true>(c, a, b, s, e, d, xa, xb);
+  mulsq_column<K, 1, true, 1>(c, a, b, s, e, d, xa, xb);     // h[K] * 977 first: < 2^43 with the carry-in (nc_bound)
   t[K] = acc_pop(c);
 }
 // r = a * b + s^2 mod p (weakly reduced): mul_add2 with a square as its second product (the doubling's Y3).  The sum is < 2^513, so
