@@ -1,0 +1,99 @@
+"""Loader for the test-only gfx950 build of the field and scalar primitives (tests/devtwin) and its host counterpart
+(tests/hosttwin, the same op tables).  Arrays are (n, words) little-endian uint32; every call checks the return code and
+raises at the first non-zero one."""
+import ctypes
+import os
+import subprocess
+
+import numpy as np
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+DEVTWIN = os.path.join(HERE, "devtwin")
+BUILDS = {"default": "libecdevtwin.so", "bf": "libecdevtwin_bf.so", "grouped": "libecdevtwin_grouped.so"}
+_LIBS = {}
+
+# op tables of tests/devtwin/primitive_ops.hpp
+K256_OPS = ["mul", "sqr", "add", "sub", "neg", "inv", "sqrt", "mul_small", "shl1", "shl2", "shl3", "mul_add2", "mul_add_sqr",
+            "half", "sub2", "normalize", "fold_top_fast", "is_zero_fast"]
+MONT_OPS = ["mul", "sqr", "add", "sub", "neg", "dbl", "half", "to_mont", "from_mont", "inv", "sqrt"]
+SCALAR_OPS = ["mul", "add", "reduce_once", "to_mont", "from_mont", "inv"]
+MONT_CURVES = ["p256", "p384"]
+SCALAR_CURVES = ["k256", "p256", "p384"]
+MAC_MAX_M = 13
+
+_P = ctypes.POINTER(ctypes.c_uint32)
+
+
+def lib(build="default"):
+    if build not in _LIBS:
+        override = os.environ.get("ECGPU_DEVTWIN_DIR")     # the same three objects built elsewhere (e.g. from a patched csrc)
+        if override:
+            _LIBS[build] = ctypes.CDLL(os.path.join(override, BUILDS[build]))
+        else:
+            subprocess.run(["make", "-s", "-C", DEVTWIN, BUILDS[build]], check=True)
+            _LIBS[build] = ctypes.CDLL(os.path.join(DEVTWIN, BUILDS[build]))
+    return _LIBS[build]
+
+
+def _ptr(a):
+    return a.ctypes.data_as(_P)
+
+
+def _in(a, words):
+    a = np.ascontiguousarray(a, dtype=np.uint32)
+    assert a.ndim == 2 and a.shape[1] == words, (a.shape, words)
+    return a
+
+
+def _check(rc, what):
+    if rc != 0:
+        raise RuntimeError(f"{what} returned {rc}")
+
+
+def k256_op(fn, op, a, b, e, f):
+    a, b, e, f = (_in(x, 8) for x in (a, b, e, f))
+    n = a.shape[0]
+    assert b.shape[0] == e.shape[0] == f.shape[0] == n
+    out = np.zeros((n, 9), dtype=np.uint32)
+    _check(fn(K256_OPS.index(op), _ptr(a), _ptr(b), _ptr(e), _ptr(f), _ptr(out), n), f"k256 {op}")
+    return out
+
+
+def mont_op(fn, curve, op, a, b):
+    w = 8 if curve == "p256" else 12
+    a, b = _in(a, w), _in(b, w)
+    n = a.shape[0]
+    assert b.shape[0] == n
+    out = np.zeros((n, w + 1), dtype=np.uint32)
+    _check(fn(MONT_CURVES.index(curve), MONT_OPS.index(op), _ptr(a), _ptr(b), _ptr(out), n), f"{curve} mont {op}")
+    return out
+
+
+def scalar_op(fn, curve, op, a, b):
+    w = 12 if curve == "p384" else 8
+    a, b = _in(a, w), _in(b, w)
+    n = a.shape[0]
+    assert b.shape[0] == n
+    out = np.zeros((n, w), dtype=np.uint32)
+    _check(fn(SCALAR_CURVES.index(curve), SCALAR_OPS.index(op), _ptr(a), _ptr(b), _ptr(out), n), f"{curve} scalar {op}")
+    return out
+
+
+def mac_cols(fn, M, fresh, nc, c, pa, pb):
+    c, pa, pb = _in(c, 3), _in(pa, MAC_MAX_M), _in(pb, MAC_MAX_M)
+    n = c.shape[0]
+    out = np.zeros((n, 3), dtype=np.uint32)
+    _check(fn(M, fresh, nc, _ptr(c), _ptr(pa), _ptr(pb), _ptr(out), n), f"mac_cols<{M}, {fresh}, {nc}>")
+    return out
+
+
+# the entry points by side: dt_* of a device build, ht_* of the host twin
+def device(build="default"):
+    L = lib(build)
+    return {"k256": L.dt_k256_op, "mont": L.dt_mont_op, "scalar": L.dt_scalar_op, "mac": L.dt_mac_cols}
+
+
+def host():
+    from hosttwin_util import lib as hlib
+    L = hlib()
+    return {"k256": L.ht_k256_prim_op, "mont": L.ht_mont_prim_op, "scalar": L.ht_scalar_op, "mac": L.ht_mac_cols}
