@@ -206,6 +206,29 @@ int ecgpu_timer_stop(ecgpu_ctx* ctx, float* milliseconds);
 int ecgpu_field_op_batch(ecgpu_ctx* ctx, int curve, int op, const uint8_t* a, const uint8_t* b,
                          uint8_t* out, size_t n, int mem);
 
+/* ---- scalar field (integers modulo the group order n) ------------------------------------------
+ * Scalar::{mul, square, add, sub, negate, invert} (k256/src/arithmetic/scalar.rs:99-209, p256/src/arithmetic/scalar.rs:99-158,
+ * p384/src/arithmetic/scalar.rs) and Field::sqrt (k256 scalar.rs:290-327, p256 scalar.rs:240-277, p384 scalar.rs:129-...).
+ * a, b, out: n canonical big-endian NB-byte scalars (the to_repr form); b is ignored (may be NULL) for unary ops.  ok may be
+ * NULL; where given, ok[i] = 1 iff the reference returns a value: an operand >= n (from_repr fails), INV of 0 (CtOption none)
+ * and SQRT of a non-residue give ok = 0 and out = 0.  SQRT returns the reference's root: its Tonelli-Shanks on k256 / p256
+ * (S = 6 / 4), a^((n+1)/4) on p384.  Constant-time: no branch or address depends on an operand; ECGPU_MEM_HOST staging of
+ * a, b and out is cleared before the call returns. */
+typedef enum ecgpu_scalar_op {
+  ECGPU_SC_MUL = 0, ECGPU_SC_SQR = 1, ECGPU_SC_ADD = 2, ECGPU_SC_SUB = 3,
+  ECGPU_SC_NEG = 4, ECGPU_SC_INV = 5, ECGPU_SC_SQRT = 6
+} ecgpu_scalar_op;
+int ecgpu_scalar_op_batch(ecgpu_ctx* ctx, int curve, int op, const uint8_t* a, const uint8_t* b,
+                          uint8_t* out, uint8_t* ok, size_t n, int mem);
+
+/* Reduce<U256 | U384 | U512> and ReduceNonZero (k256 scalar.rs:700-750, scalar/wide64.rs:120-222), and the reduction of
+ * FromOkm for Scalar (k256 | p256 | p384 src/arithmetic/hash2curve.rs: its d0 2^192 + d1 / d0 2^288 + d1 equals okm mod n).
+ * in: n big-endian records of in_bytes bytes each, 1 <= in_bytes <= 2 NB, any alignment; out: n canonical scalars.
+ * out[i] = in[i] mod n, or with ECGPU_REDUCE_NONZERO in[i] mod (n - 1) + 1.  Same hygiene and constant-time rules as above. */
+enum { ECGPU_REDUCE_NONZERO = 1u };
+int ecgpu_scalar_reduce_batch(ecgpu_ctx* ctx, int curve, const uint8_t* in, size_t in_bytes,
+                              uint8_t* out, size_t n, int mem, unsigned flags);
+
 /* ---- group law: ProjectivePoint::{add, add_mixed, double}  -------------------------------------
  * k256 projective.rs:96-161, :164-221, :225-274; primeorder point_arithmetic.rs:209-238, :247-277,
  * :286-317.  Complete formulas: total on every input, results are the exact (X, Y, Z) of the

@@ -9,6 +9,7 @@
 #include "schnorr_kernels.hpp"
 #include "h2c_kernels.hpp"
 #include "straus.hpp"
+#include "scalar_ops.hpp"
 // Results per lane that share one inversion in the wide fixed-base kernels.  With only 12-16 additions per result
 // the inversion's share is large: measured at 2^24 scalars, batch 16 / 32 / 64: p256 0.96 / 1.03 / 1.06, k256 1.19 /
 // 1.24 / 1.25 x 10^9 per second; p384 (2^22) 282 / 280 / 279 x 10^6 (its results are 144 bytes each in the private
@@ -493,10 +494,36 @@ struct CurveOps {
     HIPCHK(c, hipGetLastError());
     return 0;
   }
+  // scalar field (scalar_ops.hpp): element-wise ops one lane per element, inversions SCALAR_INV_BATCH per lane
+  static int scalar_op(ecgpu_ctx* c, int op, const u32* a, const u32* b, u32* o, uint8_t* ok, size_t n) {
+    using O = OrderOf<C>;
+    constexpr int B = SCALAR_INV_BATCH;
+    switch (op) {
+#define SOP(OPC) case OPC: hipLaunchKernelGGL((scalar_op_kernel<O, OPC>), dim3(ecgpu_grid_for(c, n, 8)), dim3(256), 0, c->stream, a, b, o, ok, n); break;
+      SOP(SC_MUL) SOP(SC_SQR) SOP(SC_ADD) SOP(SC_SUB) SOP(SC_NEG) SOP(SC_SQRT)
+#undef SOP
+      case SC_INV:
+        hipLaunchKernelGGL((scalar_inv_kernel<O, B>), dim3(ecgpu_grid_for(c, (n + B - 1) / B, 8)), dim3(256), 0, c->stream, a, o, ok, n);
+        break;
+      default: return ecgpu_set_err(c, ECGPU_ERR_ARG, "unknown scalar op %d", op);
+    }
+    HIPCHK(c, hipGetLastError());
+    return 0;
+  }
+  static int scalar_reduce(ecgpu_ctx* c, const uint8_t* in, size_t in_bytes, u32* o, size_t n, unsigned flags) {
+    using O = OrderOf<C>;
+    const unsigned g = ecgpu_grid_for(c, n, 8);
+    if (flags & SC_REDUCE_NONZERO)
+      hipLaunchKernelGGL((scalar_reduce_kernel<O, true>), dim3(g), dim3(256), 0, c->stream, in, (int)in_bytes, o, n);
+    else
+      hipLaunchKernelGGL((scalar_reduce_kernel<O, false>), dim3(g), dim3(256), 0, c->stream, in, (int)in_bytes, o, n);
+    HIPCHK(c, hipGetLastError());
+    return 0;
+  }
   static const ecgpu_curve_ops* table() {
     static const ecgpu_curve_ops t = {field_op, point_op, point_eq, normalize, lincomb, msm, validate_scalars, validate_points,
                                       decompress, synth_scalars, synth_points, to_bytes, from_bytes, sec1_encode, sec1_decode, ecdsa_verify, h2c_map, ecdsa_recover, schnorr_verify, ecdsa_sign, ecdh,
-                                      pass_units};
+                                      pass_units, scalar_op, scalar_reduce};
     return &t;
   }
 };

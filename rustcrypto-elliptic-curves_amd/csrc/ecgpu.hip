@@ -95,7 +95,7 @@ static const ecgpu_curve_ops* ops_for(int curve) {
 
 extern "C" {
 
-const char* ecgpu_version(void) { return "ecgpu 0.4 (gfx950)"; }
+const char* ecgpu_version(void) { return "ecgpu 0.5 (gfx950)"; }
 
 size_t ecgpu_field_bytes(int curve) {
   switch (curve) {
@@ -326,6 +326,26 @@ int ecgpu_field_op_batch(ecgpu_ctx* c, int curve, int op, const uint8_t* a, cons
   return finish_host(c, mem);
 }
 
+static bool scalar_op_binary(int op) { return op == ECGPU_SC_MUL || op == ECGPU_SC_ADD || op == ECGPU_SC_SUB; }
+static int scalar_op_impl(ecgpu_ctx* c, int curve, int op, const uint8_t* a, const uint8_t* b, uint8_t* out, uint8_t* ok, size_t n, int mem);
+static int scalar_reduce_impl(ecgpu_ctx* c, int curve, const uint8_t* in, size_t in_bytes, uint8_t* out, size_t n, int mem, unsigned flags);
+int ecgpu_scalar_op_batch(ecgpu_ctx* c, int curve, int op, const uint8_t* a, const uint8_t* b, uint8_t* out, uint8_t* ok, size_t n, int mem) {
+  if (!c || !a || !out) return ecgpu_set_err(c, ECGPU_ERR_ARG, "null argument");
+  if (op < ECGPU_SC_MUL || op > ECGPU_SC_SQRT) return ecgpu_set_err(c, ECGPU_ERR_ARG, "unknown scalar op %d", op);
+  if (scalar_op_binary(op) && !b) return ecgpu_set_err(c, ECGPU_ERR_ARG, "binary scalar op needs b");
+  if (n == 0) return ECGPU_OK;
+  return scalar_op_impl(c, curve, op, a, b, out, ok, n, mem);
+}
+int ecgpu_scalar_reduce_batch(ecgpu_ctx* c, int curve, const uint8_t* in, size_t in_bytes, uint8_t* out, size_t n, int mem, unsigned flags) {
+  if (!c || !in || !out) return ecgpu_set_err(c, ECGPU_ERR_ARG, "null argument");
+  const size_t nb = ecgpu_field_bytes(curve);
+  if (!nb) return ecgpu_set_err(c, ECGPU_ERR_UNSUPPORTED, "curve %d not supported", curve);
+  if (in_bytes < 1 || in_bytes > 2 * nb) return ecgpu_set_err(c, ECGPU_ERR_ARG, "in_bytes %zu outside 1 .. %zu", in_bytes, 2 * nb);
+  if (flags & ~(unsigned)ECGPU_REDUCE_NONZERO) return ecgpu_set_err(c, ECGPU_ERR_ARG, "unknown reduce flags 0x%x", flags);
+  if (n == 0) return ECGPU_OK;
+  return scalar_reduce_impl(c, curve, in, in_bytes, out, n, mem, flags);
+}
+
 static int point_op(ecgpu_ctx* c, int curve, int op, const uint8_t* p, const uint8_t* q, int q_coords, uint8_t* out, size_t n, int mem) {
   if (!c || !p || !out || (q_coords && !q)) return ecgpu_set_err(c, ECGPU_ERR_ARG, "null argument");
   if (n == 0) return ECGPU_OK;
@@ -400,6 +420,36 @@ struct SecretWipe {
     (void)hipGetLastError();
   }
 };
+
+// scalar field: operands are usually secrets, so their staged copies and the staged results are cleared on every exit path
+static int scalar_op_impl(ecgpu_ctx* c, int curve, int op, const uint8_t* a, const uint8_t* b, uint8_t* out, uint8_t* ok, size_t n, int mem) {
+  ENTER(c, curve);
+  const bool binary = scalar_op_binary(op);
+  SecretWipe wipe(c);
+  if (mem == ECGPU_MEM_HOST) { wipe.arm(0, n * nb); if (binary) wipe.arm(1, n * nb); wipe.arm(2, n * nb); wipe.arm(3, n); }
+  Buf ba, bb, bo, bk;
+  int rc;
+  if ((rc = buf_in(c, ba, 0, a, n * nb, mem))) return rc;
+  if ((rc = buf_in(c, bb, 1, binary ? b : nullptr, n * nb, mem))) return rc;
+  if ((rc = buf_out(c, bo, 2, out, n * nb, mem))) return rc;
+  if ((rc = buf_out(c, bk, 3, ok, n, mem))) return rc;
+  if ((rc = ops->scalar_op(c, op, (const uint32_t*)ba.dev, (const uint32_t*)bb.dev, (uint32_t*)bo.dev, (uint8_t*)bk.dev, n))) return rc;
+  if ((rc = buf_finish(c, bo))) return rc;
+  if ((rc = buf_finish(c, bk))) return rc;
+  return finish_host(c, mem);
+}
+static int scalar_reduce_impl(ecgpu_ctx* c, int curve, const uint8_t* in, size_t in_bytes, uint8_t* out, size_t n, int mem, unsigned flags) {
+  ENTER(c, curve);
+  SecretWipe wipe(c);
+  if (mem == ECGPU_MEM_HOST) { wipe.arm(0, n * in_bytes); wipe.arm(2, n * nb); }
+  Buf bi, bo;
+  int rc;
+  if ((rc = buf_in(c, bi, 0, in, n * in_bytes, mem))) return rc;
+  if ((rc = buf_out(c, bo, 2, out, n * nb, mem))) return rc;
+  if ((rc = ops->scalar_reduce(c, (const uint8_t*)bi.dev, in_bytes, (uint32_t*)bo.dev, n, flags))) return rc;
+  if ((rc = buf_finish(c, bo))) return rc;
+  return finish_host(c, mem);
+}
 
 static int lincomb_impl(ecgpu_ctx* c, int curve, const uint8_t* scalars, const uint8_t* points, int pt_fmt, size_t terms, uint8_t* out, int out_fmt,
                         uint8_t* out_inf, uint8_t* scalar_ok, size_t n, int mem, unsigned flags) {

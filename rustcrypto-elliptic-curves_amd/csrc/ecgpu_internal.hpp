@@ -141,6 +141,9 @@ struct ecgpu_curve_ops {
   // units of one whole pass of the kernel `lincomb` would pick: every resident lane gets its full sub-batch (the results that share
   // one inversion).  The host-buffer pipeline sizes its chunks by it (host_pipe.hpp).
   size_t (*pass_units)(const ecgpu_ctx* c, int has_points, size_t terms, unsigned flags);
+  // scalar field (scalar_ops.hpp): canonical big-endian scalars in and out; ok may be NULL
+  int (*scalar_op)(ecgpu_ctx* c, int op, const uint32_t* a, const uint32_t* b, uint32_t* out, uint8_t* ok, size_t n);
+  int (*scalar_reduce)(ecgpu_ctx* c, const uint8_t* in, size_t in_bytes, uint32_t* out, size_t n, unsigned flags);
 };
 // Pippenger MSM, one translation unit per curve (msm_*.hip); `mul` is the curve's batch scalar multiplication (affine in / out
 // on device memory), used for small sums

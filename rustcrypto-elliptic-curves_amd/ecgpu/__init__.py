@@ -33,6 +33,9 @@ K256, P256, P384 = 0, 1, 2
 CURVE_IDS = {"k256": K256, "p256": P256, "p384": P384}
 FIELD_BYTES = {K256: 32, P256: 32, P384: 48}
 FE_MUL, FE_SQR, FE_ADD, FE_SUB, FE_NEG, FE_INV, FE_SQRT = range(7)
+SC_MUL, SC_SQR, SC_ADD, SC_SUB, SC_NEG, SC_INV, SC_SQRT = range(7)      # ecgpu_scalar_op
+SC_BINARY = (SC_MUL, SC_ADD, SC_SUB)
+REDUCE_NONZERO = 1
 # ecgpu_option (per-context tuning / test knobs, include/ecgpu.h)
 OPT_FB_WINDOW, OPT_FB_MAX_WINDOW, OPT_MSM_WINDOW_BITS, OPT_MSM_SLAB_TERMS, OPT_MSM_SMALL_PATH, OPT_MSM_ROUNDS, OPT_K256_WAVES, OPT_FB_MEMORY_BUDGET, OPT_LINCOMB_TERM_BY_TERM = range(9)
 
@@ -119,6 +122,8 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
     lib.ecgpu_timer_start.argtypes = [vp]
     lib.ecgpu_timer_stop.argtypes = [vp, ctypes.POINTER(ctypes.c_float)]
     lib.ecgpu_field_op_batch.argtypes = [vp, i, i, u8p, u8p, u8p, sz, i]
+    lib.ecgpu_scalar_op_batch.argtypes = [vp, i, i, u8p, u8p, u8p, u8p, sz, i]
+    lib.ecgpu_scalar_reduce_batch.argtypes = [vp, i, u8p, sz, u8p, sz, i, ctypes.c_uint]
     lib.ecgpu_point_add_batch.argtypes = [vp, i, u8p, u8p, u8p, sz, i]
     lib.ecgpu_point_add_mixed_batch.argtypes = [vp, i, u8p, u8p, u8p, sz, i]
     lib.ecgpu_point_double_batch.argtypes = [vp, i, u8p, u8p, sz, i]
@@ -142,7 +147,7 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
     lib.ecgpu_synth_scalars.argtypes = [vp, i, ctypes.c_uint64, ctypes.c_uint64, u8p, sz]
     lib.ecgpu_synth_points.argtypes = [vp, i, ctypes.c_uint64, ctypes.c_uint64, u8p, sz]
     for name in ("ecgpu_create", "ecgpu_set_stream", "ecgpu_synchronize", "ecgpu_timer_start", "ecgpu_timer_stop",
-                 "ecgpu_field_op_batch", "ecgpu_point_add_batch", "ecgpu_point_add_mixed_batch",
+                 "ecgpu_field_op_batch", "ecgpu_scalar_op_batch", "ecgpu_scalar_reduce_batch", "ecgpu_point_add_batch", "ecgpu_point_add_mixed_batch",
                  "ecgpu_point_double_batch", "ecgpu_batch_normalize", "ecgpu_mul_batch", "ecgpu_lincomb_batch",
                  "ecgpu_msm", "ecgpu_validate_scalars", "ecgpu_validate_points", "ecgpu_decompress_batch",
                  "ecgpu_synth_scalars", "ecgpu_synth_points", "ecgpu_point_eq_batch", "ecgpu_mul_batch_checked",
@@ -161,7 +166,7 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
 
 EXPORTED_SYMBOLS = (
     "ecgpu_create", "ecgpu_destroy", "ecgpu_set_stream", "ecgpu_synchronize", "ecgpu_last_error", "ecgpu_version",
-    "ecgpu_field_bytes", "ecgpu_timer_start", "ecgpu_timer_stop", "ecgpu_field_op_batch", "ecgpu_point_add_batch",
+    "ecgpu_field_bytes", "ecgpu_timer_start", "ecgpu_timer_stop", "ecgpu_field_op_batch", "ecgpu_scalar_op_batch", "ecgpu_scalar_reduce_batch", "ecgpu_point_add_batch",
     "ecgpu_point_add_mixed_batch", "ecgpu_point_double_batch", "ecgpu_batch_normalize", "ecgpu_mul_batch",
     "ecgpu_lincomb_batch", "ecgpu_msm", "ecgpu_validate_scalars", "ecgpu_validate_points", "ecgpu_decompress_batch",
     "ecgpu_synth_scalars", "ecgpu_synth_points", "ecgpu_ecdsa_verify_batch", "ecgpu_ecdsa_sign_batch",
@@ -318,6 +323,46 @@ class Curve:
         out = _host_out(len(a), self.nb)
         pa, _ = _ptr(a); pb, _ = _ptr(bb); po, _ = _ptr(out)
         self.ctx.check(self.ctx.lib.ecgpu_field_op_batch(self.ctx.handle, self.id, op, pa, pb, po, len(a), HOST))
+        return out
+
+    # --- Scalar ------------------------------------------------------------------------------
+    def scalar_op(self, op: int, a, b=None):
+        """Scalar::{mul, square, add, sub, negate, invert, sqrt} on canonical big-endian scalars -> (out, ok); ok[i] = 0 (and
+        out[i] = 0) where the reference returns none: an operand >= n, the inverse of 0, the root of a non-residue"""
+        a = _as_host(a, self.nb)
+        if op in SC_BINARY and b is None:
+            raise ValueError("scalar op %d needs b" % op)
+        bb = _as_host(b, self.nb) if b is not None and op in SC_BINARY else None
+        if bb is not None and len(bb) != len(a):
+            raise ValueError("a and b differ in length (%d, %d)" % (len(a), len(bb)))
+        out, ok = _host_out(len(a), self.nb), np.zeros(len(a), dtype=np.uint8)
+        pa, _ = _ptr(a); pb, _ = _ptr(bb); po, _ = _ptr(out); pk, _ = _ptr(ok)
+        self.ctx.check(self.ctx.lib.ecgpu_scalar_op_batch(self.ctx.handle, self.id, op, pa, pb, po, pk, len(a), HOST))
+        return out, ok
+
+    def scalar_op_device(self, op: int, d_a, d_b, d_out, d_ok, n: int):
+        """scalar_op on device-resident scalars (torch tensors / device pointers); d_b may be None for unary ops, d_ok may be None"""
+        self._check_device(d_a, n * self.nb, "d_a")
+        if op in SC_BINARY:
+            if d_b is None:
+                raise ValueError("scalar op %d needs d_b" % op)
+            self._check_device(d_b, n * self.nb, "d_b")
+        self._check_device(d_out, n * self.nb, "d_out")
+        self._check_device(d_ok, n, "d_ok")
+        self.ctx.check(self.ctx.lib.ecgpu_scalar_op_batch(self.ctx.handle, self.id, op, _ptr(d_a)[0], _ptr(d_b if op in SC_BINARY else None)[0],
+                                                          _ptr(d_out)[0], _ptr(d_ok)[0], n, DEVICE))
+
+    def scalar_reduce(self, data, nonzero: bool = False, in_bytes: Optional[int] = None) -> np.ndarray:
+        """Reduce / ReduceNonZero / FromOkm: big-endian records of in_bytes bytes (1 .. 2 NB; default: the width of a 2-D
+        array's rows) -> canonical scalars, int mod n or, with nonzero, int mod (n - 1) + 1"""
+        if in_bytes is None:
+            if not (isinstance(data, np.ndarray) and data.ndim == 2):
+                raise ValueError("in_bytes is needed unless data is an (n, in_bytes) array")
+            in_bytes = data.shape[1]
+        d = _as_host(data, in_bytes)
+        out = _host_out(len(d), self.nb)
+        self.ctx.check(self.ctx.lib.ecgpu_scalar_reduce_batch(self.ctx.handle, self.id, _ptr(d)[0], in_bytes, _ptr(out)[0], len(d), HOST,
+                                                              REDUCE_NONZERO if nonzero else 0))
         return out
 
     # --- ProjectivePoint::{add, add_mixed, double}, BatchNormalize ------------------------------

@@ -36,6 +36,16 @@ pub const ECGPU_FE_SUB: c_int = 3;
 pub const ECGPU_FE_NEG: c_int = 4;
 pub const ECGPU_FE_INV: c_int = 5;
 pub const ECGPU_FE_SQRT: c_int = 6;
+/// `ecgpu_scalar_op`: Scalar::{mul, square, add, sub, negate, invert} and Field::sqrt modulo the group order
+pub const ECGPU_SC_MUL: c_int = 0;
+pub const ECGPU_SC_SQR: c_int = 1;
+pub const ECGPU_SC_ADD: c_int = 2;
+pub const ECGPU_SC_SUB: c_int = 3;
+pub const ECGPU_SC_NEG: c_int = 4;
+pub const ECGPU_SC_INV: c_int = 5;
+pub const ECGPU_SC_SQRT: c_int = 6;
+/// `ecgpu_scalar_reduce_batch`: ReduceNonZero (int mod (n - 1) + 1) instead of Reduce (int mod n)
+pub const ECGPU_REDUCE_NONZERO: c_uint = 1;
 /// the reference's own schedule, constant-time table scans included: exact (X, Y, Z), and the one for secret scalars
 pub const ECGPU_EXACT_REFERENCE: c_uint = 1;
 /// the k256 low-s rules of k256/src/ecdsa.rs:182-207
@@ -80,6 +90,10 @@ extern "C" {
     pub fn ecgpu_timer_start(ctx: *mut ecgpu_ctx) -> c_int;
     pub fn ecgpu_timer_stop(ctx: *mut ecgpu_ctx, milliseconds: *mut f32) -> c_int;
     pub fn ecgpu_field_op_batch(ctx: *mut ecgpu_ctx, curve: c_int, op: c_int, a: *const u8, b: *const u8, out: *mut u8, n: usize, mem: c_int) -> c_int;
+    pub fn ecgpu_scalar_op_batch(ctx: *mut ecgpu_ctx, curve: c_int, op: c_int, a: *const u8, b: *const u8, out: *mut u8, ok: *mut u8, n: usize,
+                                 mem: c_int) -> c_int;
+    pub fn ecgpu_scalar_reduce_batch(ctx: *mut ecgpu_ctx, curve: c_int, input: *const u8, in_bytes: usize, out: *mut u8, n: usize, mem: c_int,
+                                     flags: c_uint) -> c_int;
     pub fn ecgpu_point_add_batch(ctx: *mut ecgpu_ctx, curve: c_int, p_xyz: *const u8, q_xyz: *const u8, out_xyz: *mut u8, n: usize, mem: c_int) -> c_int;
     pub fn ecgpu_point_add_mixed_batch(ctx: *mut ecgpu_ctx, curve: c_int, p_xyz: *const u8, q_xy: *const u8, out_xyz: *mut u8, n: usize, mem: c_int) -> c_int;
     pub fn ecgpu_point_double_batch(ctx: *mut ecgpu_ctx, curve: c_int, p_xyz: *const u8, out_xyz: *mut u8, n: usize, mem: c_int) -> c_int;
@@ -188,6 +202,30 @@ impl Context {
         let n = a.len() / nb;
         let mut out = vec![0u8; a.len()];
         self.check(unsafe { ecgpu_field_op_batch(self.0, curve, op, a.as_ptr(), b.map_or(core::ptr::null(), |b| b.as_ptr()), out.as_mut_ptr(), n, ECGPU_MEM_HOST) })?;
+        Ok(out)
+    }
+    /// Scalar op on `n` canonical big-endian scalars (`a`, `b` for the binary ops and the result are `n * NB` bytes), with one
+    /// `ok` byte per element: 0 where the reference returns none (operand >= n, inverse of 0, root of a non-residue; out is 0 there).
+    pub fn scalar_op(&self, curve: c_int, op: c_int, a: &[u8], b: Option<&[u8]>) -> Result<(Vec<u8>, Vec<u8>), Error> {
+        let nb = Self::field_bytes(curve);
+        let binary = op == ECGPU_SC_MUL || op == ECGPU_SC_ADD || op == ECGPU_SC_SUB;
+        Self::arg(nb != 0 && a.len() % nb == 0 && (!binary || b.map_or(false, |b| b.len() == a.len())))?;
+        let n = a.len() / nb;
+        let mut out = vec![0u8; a.len()];
+        let mut ok = vec![0u8; n];
+        let bp = if binary { b.map_or(core::ptr::null(), |b| b.as_ptr()) } else { core::ptr::null() };
+        self.check(unsafe { ecgpu_scalar_op_batch(self.0, curve, op, a.as_ptr(), bp, out.as_mut_ptr(), ok.as_mut_ptr(), n, ECGPU_MEM_HOST) })?;
+        Ok((out, ok))
+    }
+    /// Reduce / ReduceNonZero / FromOkm: `input` holds records of `in_bytes` (1 ..= 2 NB) big-endian bytes; one canonical
+    /// scalar per record (int mod n, or int mod (n - 1) + 1 with `nonzero`).
+    pub fn scalar_reduce(&self, curve: c_int, input: &[u8], in_bytes: usize, nonzero: bool) -> Result<Vec<u8>, Error> {
+        let nb = Self::field_bytes(curve);
+        Self::arg(nb != 0 && in_bytes >= 1 && in_bytes <= 2 * nb && input.len() % in_bytes == 0)?;
+        let n = input.len() / in_bytes;
+        let mut out = vec![0u8; n * nb];
+        let flags = if nonzero { ECGPU_REDUCE_NONZERO } else { 0 };
+        self.check(unsafe { ecgpu_scalar_reduce_batch(self.0, curve, input.as_ptr(), in_bytes, out.as_mut_ptr(), n, ECGPU_MEM_HOST, flags) })?;
         Ok(out)
     }
     /// ProjectivePoint + ProjectivePoint, X || Y || Z per point.

@@ -6,7 +6,8 @@
 //! (field.rs:118-120, field_5x52.rs:96-131), `Scalar::to_bytes` (scalar.rs:94-96); nothing here depends on the in-memory
 //! layout of the types (which is not ABI-stable, field_impl.rs:23-28).
 use alloc::vec::Vec;
-use ecgpu_sys::{Context, Error, Group, ECGPU_EXACT_REFERENCE, ECGPU_K256, ECGPU_PT_AFFINE, ECGPU_PT_PROJECTIVE};
+use ecgpu_sys::{Context, Error, Group, ECGPU_EXACT_REFERENCE, ECGPU_K256, ECGPU_PT_AFFINE, ECGPU_PT_PROJECTIVE, ECGPU_SC_INV};
+use elliptic_curve::{ff::PrimeField, subtle::{Choice, CtOption}};
 
 use crate::{AffinePoint, FieldBytes, ProjectivePoint, Scalar};
 use super::FieldElement;
@@ -30,6 +31,23 @@ fn put_scalars<'a>(it: impl Iterator<Item = &'a Scalar>) -> Vec<u8> {
     let mut v = Vec::new();
     for k in it { v.extend_from_slice(&k.to_bytes()); }
     v
+}
+
+/// Bulk `Scalar::invert` (scalar.rs:161-209): one `CtOption` per scalar, none for 0 as on the CPU path.  Constant-time
+/// kernel (csrc/scalar_ops.hpp: a lane shares one Fermat inversion over its batch with masks, no branch on a value), so it
+/// serves `invert_vartime` callers as well.
+pub fn invert_batch(gpu: &Context, scalars: &[Scalar]) -> Result<Vec<CtOption<Scalar>>, Error> {
+    let s = put_scalars(scalars.iter());
+    let (out, ok) = gpu.scalar_op(ECGPU_K256, ECGPU_SC_INV, &s, None)?;
+    Ok(out
+        .chunks_exact(32)
+        .zip(ok.iter())
+        .map(|(b, &k)| {
+            // the library only returns canonical scalars: from_repr cannot fail on them
+            let v = Scalar::from_repr(*FieldBytes::from_slice(b)).unwrap();
+            CtOption::new(v, Choice::from(k))
+        })
+        .collect())
 }
 
 /// Bulk `MulByGenerator::mul_by_generator` (mul.rs:415-440): out[i] = scalars[i] * G, the exact (X, Y, Z) the CPU path

@@ -1,5 +1,9 @@
-"""Throughput of the secondary entry points (SURVEY.md 8f rows and the element-wise field / point ops) on device-resident
-batches: python tools/util_bench.py [log2n]   -> one line per (curve, operation), M elements/s"""
+"""Throughput of the secondary entry points (SURVEY.md 8f rows and the element-wise field / point / scalar ops) on device-resident
+batches: python tools/util_bench.py [log2n] [--scalar]   -> one line per (curve, operation), M elements/s
+
+--scalar: the scalar-field rows only (ecgpu_scalar_op_batch, ecgpu_scalar_reduce_batch), plus the scalar inversion of every
+SCALAR_INV_BATCH variant found in rustcrypto-elliptic-curves_amd/lib_exp/libecgpu_inv<B>_<curve>.so, built by
+    make -C rustcrypto-elliptic-curves_amd variant NAME=inv<B>_<curve> TU=ops_<curve> DEFS=-DSCALAR_INV_BATCH=<B>"""
 import ctypes
 import os
 import sys
@@ -9,7 +13,9 @@ import torch
 import ecgpu
 from oracle import synth
 
-lg = int(sys.argv[1]) if len(sys.argv) > 1 else 20
+args = [a for a in sys.argv[1:] if not a.startswith("--")]
+SCALAR_ONLY = "--scalar" in sys.argv
+lg = int(args[0]) if args else 20
 n = 1 << lg
 ctx = ecgpu.Context(0)
 lib, h = ctx.lib, ctx.handle
@@ -20,15 +26,49 @@ def P(t):
     return vp(t.data_ptr()) if t is not None else None
 
 
-def timed(name, cn, fn, reps=3):
+def timed(name, cn, fn, reps=3, lib=lib, h=h):
     best = 1e9
     for _ in range(reps):
-        ctx.timer_start()
+        assert lib.ecgpu_timer_start(h) == 0
         rc = fn()
-        ms = ctx.timer_stop()
+        ms = ctypes.c_float()
+        assert lib.ecgpu_timer_stop(h, ctypes.byref(ms)) == 0
         assert rc in (0, None), (name, rc, lib.ecgpu_last_error(h))
-        best = min(best, ms)
+        best = min(best, ms.value)
     print(f"{cn:5s} {name:34s} n=2^{lg}  {best:8.3f} ms  {n / best / 1e3:9.2f} M/s", flush=True)
+
+
+SC_NAMES = ("mul", "sqr", "add", "sub", "neg", "invert", "sqrt")
+
+
+def scalar_rows(cn, cid, nb, s, s2):
+    """every scalar op and the reductions on device-resident scalars s, s2 (n x NB, valid)"""
+    u8 = dict(dtype=torch.uint8, device="cuda")
+    so, sk = torch.empty((n, nb), **u8), torch.empty((n,), **u8)
+    for op, nm in enumerate(SC_NAMES):
+        timed("scalar " + nm, cn, lambda op=op: lib.ecgpu_scalar_op_batch(h, cid, op, P(s), P(s2), P(so), P(sk), n, 1))
+    for width, nm in ((nb, "scalar reduce (NB bytes)"), (2 * nb, "scalar reduce (2 NB bytes)"), (72 if nb == 48 else 48, "scalar reduce (FromOkm width)")):
+        wide = torch.cat([s, s2], 1)[:, :width].contiguous()
+        timed(nm, cn, lambda w=wide, width=width: lib.ecgpu_scalar_reduce_batch(h, cid, P(w), width, P(so), n, 1, 0))
+        timed(nm.replace("reduce", "reduce_nonzero"), cn, lambda w=wide, width=width: lib.ecgpu_scalar_reduce_batch(h, cid, P(w), width, P(so), n, 1, 1))
+    # the inversion at each SCALAR_INV_BATCH variant: a context of that library build on the same device buffers, checked against
+    # the default build
+    exp = os.path.join(ROOT, "rustcrypto-elliptic-curves_amd", "lib_exp")
+    for b in (1, 8, 16, 32):
+        path = os.path.join(exp, "libecgpu_inv%d_%s.so" % (b, cn))
+        if not os.path.exists(path):
+            continue
+        vlib = ecgpu.load_library(path)
+        vh = vp()
+        assert vlib.ecgpu_create(ctypes.byref(vh), 0) == 0
+        timed("scalar invert, SCALAR_INV_BATCH=%d" % b, cn, lambda: vlib.ecgpu_scalar_op_batch(vh, cid, 5, P(s), None, P(so), P(sk), n, 1),
+              lib=vlib, h=vh)
+        assert vlib.ecgpu_synchronize(vh) == 0
+        ref = torch.empty_like(so)
+        assert lib.ecgpu_scalar_op_batch(h, cid, 5, P(s), None, P(ref), None, n, 1) == 0
+        ctx.synchronize()
+        assert bool((ref == so).all()), "SCALAR_INV_BATCH=%d differs from the default build" % b
+        vlib.ecgpu_destroy(vh)
 
 
 for cn in ("k256", "p256", "p384"):
@@ -41,6 +81,11 @@ for cn in ("k256", "p256", "p384"):
     cv.synth_scalars_device(s, n, synth.SEED, 0); cv.synth_scalars_device(s2, n, synth.SEED + 1, 0)
     cv.synth_points_device(p, n, synth.SEED, 0)
     ctx.synchronize()
+    scalar_rows(cn, cid, nb, s, s2)
+    if SCALAR_ONLY:
+        del s, s2, p, o, o2
+        torch.cuda.empty_cache()
+        continue
     x = p[:, :nb].contiguous(); y = p[:, nb:].contiguous()
     fo = torch.empty((n, nb), **u8)
     for op, nm in ((0, "field mul"), (1, "field sqr"), (2, "field add"), (5, "field invert"), (6, "field sqrt")):
