@@ -20,6 +20,9 @@ static int stage_reserve(ecgpu_ctx* c, int slot, size_t bytes) {
   size_t cap = bytes + bytes / 4 + 256;
   HIPCHK(c, hipMalloc(&c->stage[slot], cap));
   c->stage_cap[slot] = cap;
+  // recycled memory keeps its old contents: a slot starts out zero, its slack included (waited for: the pipeline's own streams use it next)
+  HIPCHK(c, hipMemsetAsync(c->stage[slot], 0, cap, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
   return 0;
 }
 

@@ -33,6 +33,7 @@ namespace jac {
 
 template <class C> ECGPU_HD void set_infinity(Jac<C>& p) { C::fe_zero(p.x); C::fe_zero(p.y); C::fe_zero(p.z); }
 template <class C> ECGPU_HD void fe_dbl(typename C::Fe& r, const typename C::Fe& a) { C::fe_add(r, a, a); }
+template <class C> ECGPU_HD bool z_is_one(const typename C::Fe& z) { typename C::Fe o, d; C::fe_one(o); C::fe_sub(d, z, o); return C::fe_is_zero(d); }   // for the ECGPU_EXC_NOTE conditions only
 
 // In-place doubling.  a = 0 (k256): 3M + 4S.  a = -3 (NIST): 4M + 4S (dbl-2004-hmv).
 template <class C>
@@ -84,6 +85,7 @@ template <class C>
 ECGPU_HD void add_mixed(Jac<C>& p, const typename C::Fe& x2, const typename C::Fe& y2) {
   using Fe = typename C::Fe;
   if (C::fe_is_zero_fast(p.z)) {
+    ECGPU_EXC_NOTE("jac.add_mixed.inf", true);
     p.x = x2; p.y = y2; C::fe_one(p.z);
     return;
   }
@@ -95,9 +97,13 @@ ECGPU_HD void add_mixed(Jac<C>& p, const typename C::Fe& x2, const typename C::F
   C::fe_sub(r, r, p.y);
   if (__builtin_expect(C::fe_is_zero_fast(h), 0)) {
     if (C::fe_is_zero(r)) {               // same point
+      ECGPU_EXC_NOTE("jac.add_mixed.same", true);
+      ECGPU_EXC_NOTE("jac.add_mixed.same:z", !z_is_one<C>(p.z));
       p.x = x2; p.y = y2; C::fe_one(p.z);
       dbl<C>(p);
     } else {                              // opposite points
+      ECGPU_EXC_NOTE("jac.add_mixed.opp", true);
+      ECGPU_EXC_NOTE("jac.add_mixed.opp:z", !z_is_one<C>(p.z));
       set_infinity<C>(p);
     }
     return;
@@ -121,6 +127,8 @@ ECGPU_HD void add_affine(Jac<C>& p, const typename C::Fe& x2, const typename C::
   C::fe_sub(h, x2, p.x);
   C::fe_sub(r, y2, p.y);
   if (__builtin_expect(C::fe_is_zero_fast(h), 0)) {
+    ECGPU_EXC_NOTE("jac.add_affine.same", C::fe_is_zero(r));
+    ECGPU_EXC_NOTE("jac.add_affine.opp", !C::fe_is_zero(r));
     if (C::fe_is_zero(r)) dbl<C>(p);      // same point (Z = 1 already)
     else set_infinity<C>(p);              // opposite points
     return;
@@ -185,8 +193,8 @@ ECGPU_HD void coz_add_update(typename C::Fe& rx, typename C::Fe& ry, typename C:
 template <class C>
 ECGPU_HD void add(Jac<C>& r, const Jac<C>& p, const Jac<C>& q) {
   using Fe = typename C::Fe;
-  if (C::fe_is_zero_fast(p.z)) { r = q; return; }
-  if (C::fe_is_zero_fast(q.z)) { r = p; return; }
+  if (C::fe_is_zero_fast(p.z)) { ECGPU_EXC_NOTE("jac.add.p_inf", true); r = q; return; }
+  if (C::fe_is_zero_fast(q.z)) { ECGPU_EXC_NOTE("jac.add.q_inf", true); r = p; return; }
   Fe z1z1, z2z2, u1, u2, s1, s2, h, rr, t;
   C::fe_sqr(z1z1, p.z); C::fe_sqr(z2z2, q.z);
   C::fe_mul(u1, p.x, z2z2); C::fe_mul(u2, q.x, z1z1);
@@ -195,6 +203,10 @@ ECGPU_HD void add(Jac<C>& r, const Jac<C>& p, const Jac<C>& q) {
   C::fe_sub(h, u2, u1);
   C::fe_sub(rr, s2, s1);
   if (C::fe_is_zero_fast(h)) {
+    ECGPU_EXC_NOTE("jac.add.same", C::fe_is_zero(rr));
+    ECGPU_EXC_NOTE("jac.add.same:z", C::fe_is_zero(rr) && !z_is_one<C>(p.z));
+    ECGPU_EXC_NOTE("jac.add.opp", !C::fe_is_zero(rr));
+    ECGPU_EXC_NOTE("jac.add.opp:z", !C::fe_is_zero(rr) && !z_is_one<C>(p.z));
     if (C::fe_is_zero(rr)) { r = p; dbl<C>(r); return; }
     set_infinity<C>(r);
     return;

@@ -346,7 +346,7 @@ __device__ __forceinline__ void k256_fast_finish(const JacK256* res, FeK256* pre
 // Two-term linear combination k0*P0 + k1*P1 sharing the 128 doublings (LinearCombination::lincomb,
 // k256 mul.rs:313-323 with N = 2: the ECDSA-verify shape u1*G + u2*Q).  Each term gets its own common-Z
 // table; the two tables live on curves isomorphic by different factors, so each is rescaled by the other's
-// factor (x u^2, y u^3) to put both on the curve isomorphic by zfix0 * zfix1.
+// factor (x u^2, y u^3) to put both on the curve isomorphic by zfix0 * zfix1.  (tests/hosttwin/hosttwin_k256.cpp::ht_k256_lincomb2_fast restates this lane body: keep it in step.)
 template <int WB>
 __device__ __forceinline__ void k256_fast_rescale(TabSlotK256* tab, const FeK256& s) {
   FeK256 s2, s3;

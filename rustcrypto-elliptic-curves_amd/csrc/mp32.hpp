@@ -35,6 +35,13 @@
 #ifndef ECGPU_TABLE_TOUCH
 #define ECGPU_TABLE_TOUCH(idx) ((void)0)
 #endif
+// Hook at every exceptional case of the incomplete point additions (accumulator or addend at infinity, the same point, opposite
+// points; "...:z" again while the accumulator's Z has left 1): empty in the product, and `cond` is NOT evaluated there.  The
+// test-only host build counts, per site name, how often `cond` holds, which is how the tests show that their related-point inputs
+// (tests/related_point_vectors.py) really enter these branches.
+#ifndef ECGPU_EXC_NOTE
+#define ECGPU_EXC_NOTE(site, cond) ((void)0)
+#endif
 
 namespace ecgpu {
 

@@ -56,6 +56,7 @@ template <class C>
 ECGPU_HD void xyzz_add_mixed(Xyzz<C>& p, const typename C::Fe& x2, const typename C::Fe& y2) {
   using Fe = typename C::Fe;
   if (C::fe_is_zero_fast(p.zz)) {
+    ECGPU_EXC_NOTE("msm.xyzz_add_mixed.inf", true);
     p.x = x2; p.y = y2; C::fe_one(p.zz); C::fe_one(p.zzz);
     return;
   }
@@ -63,6 +64,10 @@ ECGPU_HD void xyzz_add_mixed(Xyzz<C>& p, const typename C::Fe& x2, const typenam
   C::fe_mul(pp, x2, p.zz); C::fe_sub(pp, pp, p.x);           // P = U2 - X1
   C::fe_mul(r, y2, p.zzz); C::fe_sub(r, r, p.y);             // R = S2 - Y1
   if (__builtin_expect(C::fe_is_zero_fast(pp), 0)) {
+    ECGPU_EXC_NOTE("msm.xyzz_add_mixed.same", C::fe_is_zero(r));
+    ECGPU_EXC_NOTE("msm.xyzz_add_mixed.same:z", C::fe_is_zero(r) && !jac::z_is_one<C>(p.zz));
+    ECGPU_EXC_NOTE("msm.xyzz_add_mixed.opp", !C::fe_is_zero(r));
+    ECGPU_EXC_NOTE("msm.xyzz_add_mixed.opp:z", !C::fe_is_zero(r) && !jac::z_is_one<C>(p.zz));
     if (C::fe_is_zero(r)) {                       // same point: 2 (x2, y2), brought from Jacobian (X, Y, Z) to (X, Y, Z^2, Z^3)
       Jac<C> d;
       d.x = x2; d.y = y2; C::fe_one(d.z);
@@ -120,14 +125,18 @@ ECGPU_HD void jacobian_to_xyzz(Xyzz<C>& r, const Jac<C>& p);
 template <class C>
 ECGPU_HD void xyzz_add(Xyzz<C>& p, const Xyzz<C>& q) {
   using Fe = typename C::Fe;
-  if (C::fe_is_zero_fast(q.zz)) return;
-  if (C::fe_is_zero_fast(p.zz)) { p = q; return; }
+  if (C::fe_is_zero_fast(q.zz)) { ECGPU_EXC_NOTE("msm.xyzz_add.q_inf", true); return; }
+  if (C::fe_is_zero_fast(p.zz)) { ECGPU_EXC_NOTE("msm.xyzz_add.p_inf", true); p = q; return; }
   Fe u1, u2, s1, s2, pp, t;
   C::fe_mul(u1, p.x, q.zz); C::fe_mul(u2, q.x, p.zz);
   C::fe_mul(s1, p.y, q.zzz); C::fe_mul(s2, q.y, p.zzz);
   C::fe_sub(u2, u2, u1);                                     // P = U2 - U1
   C::fe_sub(s2, s2, s1);                                     // R = S2 - S1
   if (__builtin_expect(C::fe_is_zero_fast(u2), 0)) {
+    ECGPU_EXC_NOTE("msm.xyzz_add.same", C::fe_is_zero(s2));
+    ECGPU_EXC_NOTE("msm.xyzz_add.same:z", C::fe_is_zero(s2) && !jac::z_is_one<C>(p.zz));
+    ECGPU_EXC_NOTE("msm.xyzz_add.opp", !C::fe_is_zero(s2));
+    ECGPU_EXC_NOTE("msm.xyzz_add.opp:z", !C::fe_is_zero(s2) && !jac::z_is_one<C>(p.zz));
     if (C::fe_is_zero(s2)) {                                 // the same point: 2 p through (X ZZ, Y ZZZ, ZZ)
       Jac<C> d;
       C::fe_mul(d.x, p.x, p.zz); C::fe_mul(d.y, p.y, p.zzz); d.z = p.zz;

@@ -110,6 +110,8 @@ ECGPU_HD void jac_double_affine(JacK256& r, const FeK256& x, const FeK256& y) {
   jac_double(r);
 }
 
+ECGPU_HD bool z_is_one(const FeK256& z) { FeK256 o; set_one(o); return equal(z, o); }   // for the ECGPU_EXC_NOTE conditions only
+
 // In-place p += (x2, y2) for an affine, non-identity (x2, y2).  8M + 3S.  `zr` (optional) receives
 // the ratio Z3 / Z1 = H, which the table construction needs.  Real control flow (not selects) for
 // the special cases so that no second copy of the accumulator has to stay live:
@@ -118,6 +120,7 @@ ECGPU_HD void jac_double_affine(JacK256& r, const FeK256& x, const FeK256& y) {
 //   same x, opposite y       -> Z3 = Z1 * 0 = 0: infinity falls out of the formula
 ECGPU_HD void jac_add_mixed(JacK256& p, const FeK256& x2, const FeK256& y2, FeK256* zr) {
   if (is_zero_fast(p.z)) {
+    ECGPU_EXC_NOTE("k256.jac_add_mixed.inf", true);
     p.x = x2; p.y = y2; set_one(p.z);
     if (zr) set_one(*zr);
     return;
@@ -129,10 +132,14 @@ ECGPU_HD void jac_add_mixed(JacK256& p, const FeK256& x2, const FeK256& y2, FeK2
   sub(h, h, p.x);                            // H
   sub(r, r, p.y);                            // R
   if (__builtin_expect(is_zero_fast(h) && is_zero(r), 0)) {   // never taken for honest GLV digits; kept exact
+    ECGPU_EXC_NOTE("k256.jac_add_mixed.same", true);
+    ECGPU_EXC_NOTE("k256.jac_add_mixed.same:z", !z_is_one(p.z));
     if (zr) dbl(*zr, y2);
     jac_double_affine(p, x2, y2);
     return;
   }
+  ECGPU_EXC_NOTE("k256.jac_add_mixed.opp", is_zero(h));                         // no branch of its own: Z3 = Z1 * 0
+  ECGPU_EXC_NOTE("k256.jac_add_mixed.opp:z", is_zero(h) && !z_is_one(p.z));
   if (zr) *zr = h;
   mul(p.z, p.z, h);                          // Z3
   sqr(t, h);                                 // HH

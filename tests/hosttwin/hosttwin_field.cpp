@@ -54,3 +54,17 @@ extern "C" size_t ht_trace_stop(int* out, size_t cap) {
   for (size_t i = 0; i < g_trace.size() && i < cap; i++) out[i] = g_trace[i];
   return g_trace.size();
 }
+
+// ---- exceptional-case counters (hosttwin_trace.hpp): every ECGPU_EXC_NOTE of this library whose condition holds lands here ----
+#include <map>
+#include <string>
+static std::map<std::string, size_t> g_exc;
+extern "C" void ht_exc_push(const char* site) { g_exc[site]++; }
+extern "C" void ht_exc_reset(void) { g_exc.clear(); }
+// writes "site=count\n" for every site hit since the last reset (truncated at cap - 1 characters, NUL-terminated); returns the length needed
+extern "C" size_t ht_exc_counts(char* out, size_t cap) {
+  std::string s;
+  for (const auto& kv : g_exc) s += kv.first + "=" + std::to_string(kv.second) + "\n";
+  if (cap) { const size_t m = s.size() < cap - 1 ? s.size() : cap - 1; memcpy(out, s.data(), m); out[m] = 0; }
+  return s.size();
+}

@@ -130,6 +130,78 @@ int ht_k256_mul_fast(const uint8_t* pts, int proj, const uint8_t* ks, uint8_t* o
 int ht_k256_mul_fast_w(int wb, const uint8_t* pts, int proj, const uint8_t* ks, uint8_t* out, int n, int batch) {
   return wb == 4 ? mul_fast_walk<4>(pts, proj, ks, out, n, batch) : mul_fast_walk<5>(pts, proj, ks, out, n, batch);
 }
+// The lane body of the two-term throughput kernel (k256_lincomb2_fast_kernel, kernels.hpp) restated unit by unit as
+// mul_fast_walk restates the single-term one: per term the prep (GLV split, 4-bit recoding, common-Z table), each table rescaled
+// by the OTHER term's zfix so that both sit on the curve isomorphic by zfix0 * zfix1, then the shared window loop with four
+// add_digit calls per position.  out[i] = k[2i] P[2i] + k[2i+1] P[2i+1] as x||y||inf (65 B).
+int ht_k256_lincomb2_fast(const uint8_t* pts, int proj, const uint8_t* ks, uint8_t* out, int n, int batch) {
+  constexpr int WB = 4, SLOTS = K256Win<WB>::SLOTS, NPOS = K256Win<WB>::NPOS, NE = K256Win<WB>::NE, SS = K256_SLOT_STRIDE;
+  TabSlotK256 tab[2 * SLOTS];
+  JacK256* res = (JacK256*)malloc(sizeof(JacK256) * batch);
+  FeK256* pre = (FeK256*)malloc(sizeof(FeK256) * batch * 3);
+  u32* inf = (u32*)malloc(sizeof(u32) * batch);
+  const int pw = proj ? 96 : 64;
+  for (int base = 0; base < n; base += batch) {
+    int cnt = (n - base < batch) ? n - base : batch;
+    for (int j = 0; j < cnt; j++) {
+      u32 w[2][2][K256_DW];
+      bool neg[2][2], p_inf[2];
+      FeK256 zfix[2];
+      for (int t = 0; t < 2; t++) {
+        const size_t term = 2 * (size_t)(base + j) + t;
+        u32 k[8]; load_scalar(k, ks + 32 * term);
+        k256::scalar_reduce_once(k);
+        k256::GlvSplit s; k256::glv_split(s, k);
+        k256::recode_half<WB>(w[t][0], s.k1); k256::recode_half<WB>(w[t][1], s.k2);
+        neg[t][0] = s.neg1; neg[t][1] = s.neg2;
+        const uint8_t* src = pts + (size_t)pw * term;
+        FeK256 px, py, pz; load(px, src); load(py, src + 32);
+        if (proj) {
+          load(pz, src + 64); p_inf[t] = k256::is_zero(pz);
+          FeK256 zz; k256::mul(px, px, pz); k256::sqr(zz, pz); k256::mul(py, py, zz);
+        } else {
+          int z = 1; for (int b = 0; b < 64; b++) z &= (src[b] == 0);
+          p_inf[t] = z; k256::set_one(pz);
+        }
+        if (p_inf[t]) { PtK256 g; k256::generator(g); px = g.x; py = g.y; k256::set_one(pz); }
+        FeK256 zg;
+        k256::table_build_globalz<WB>(tab + t * SLOTS, zg, px, py);
+        k256::mul(zfix[t], zg, pz);
+      }
+      for (int t = 0; t < 2; t++) {                      // k256_fast_rescale: (x u^2, y u^3) with u = the other table's zfix
+        FeK256 s2, s3; k256::sqr(s2, zfix[1 - t]); k256::mul(s3, s2, zfix[1 - t]);
+        TabSlotK256* tb = tab + t * SLOTS;
+        for (int e = 0; e < NE; e++) {
+          FeK256 y;
+          k256::mul(tb[SS * e].x, tb[SS * e].x, s2);
+          k256::mul(y, tb[SS * e].y, s3);
+          tb[SS * e].y = y;
+          if (SS == 2) { k256::mul(tb[SS * e + 1].x, tb[SS * e + 1].x, s2); tb[SS * e + 1].y = y; }
+        }
+      }
+      JacK256 acc;
+      k256::set_zero(acc.x); k256::set_zero(acc.y); k256::set_zero(acc.z);
+      for (int pos = NPOS - 1; pos >= 0; pos--) {
+        if (pos != NPOS - 1) for (int d = 0; d < WB; d++) k256::jac_double(acc);
+        for (int h = 0; h < 4; h++) {
+          int dg = k256::half_digit<WB>(w[h >> 1][h & 1], pos);
+          if (p_inf[h >> 1]) dg = 0;
+          k256::add_digit(acc, tab + (h >> 1) * SLOTS, dg, (h & 1) != 0, neg[h >> 1][h & 1]);
+        }
+      }
+      FeK256 zf; k256::mul(zf, zfix[0], zfix[1]);
+      k256::mul(acc.z, acc.z, zf);
+      res[j] = acc;
+    }
+    k256::jac_batch_to_affine<0>(pre + batch, pre + 2 * batch, inf, res, cnt, pre);
+    for (int j = 0; j < cnt; j++) {
+      uint8_t* o = out + 65 * (size_t)(base + j);
+      store(o, pre[batch + j]); store(o + 32, pre[2 * batch + j]); o[64] = (uint8_t)inf[j];
+    }
+  }
+  free(res); free(pre); free(inf);
+  return 0;
+}
 // r = P + Q with P Jacobian (X||Y||Z, x = X/Z^2) and Q affine: out Jacobian X||Y||Z (canonical bytes)
 int ht_k256_jac_add_mixed(const uint8_t* p, const uint8_t* q, uint8_t* out, int n) {
   for (int i = 0; i < n; i++) {

@@ -231,6 +231,25 @@ extern "C" int ht_xyzz_add_mixed(int curve, const uint8_t* p, const uint8_t* q, 
   return curve == 1 ? xyzz_op<CurveP256>(p, q, out, n) : xyzz_op<CurveP384>(p, q, out, n);
 }
 
+// the general XYZZ addition on its own: p, q = X||Y||ZZ||ZZZ (ZZ = 0: infinity), out = the Jacobian triple X||Y||Z of p + q
+template <class C>
+static int xyzz_add_op(const uint8_t* p, const uint8_t* q, uint8_t* out, int n) {
+  for (int i = 0; i < n; i++) {
+    msm::Xyzz<C> a, b;
+    load<C>(a.x, p + 4 * C::NB * i); load<C>(a.y, p + 4 * C::NB * i + C::NB); load<C>(a.zz, p + 4 * C::NB * i + 2 * C::NB); load<C>(a.zzz, p + 4 * C::NB * i + 3 * C::NB);
+    load<C>(b.x, q + 4 * C::NB * i); load<C>(b.y, q + 4 * C::NB * i + C::NB); load<C>(b.zz, q + 4 * C::NB * i + 2 * C::NB); load<C>(b.zzz, q + 4 * C::NB * i + 3 * C::NB);
+    msm::xyzz_add<C>(a, b);
+    Jac<C> r;
+    msm::xyzz_to_jacobian<C>(r, a);
+    store_jac<C>(out + 3 * C::NB * i, r);
+  }
+  return 0;
+}
+extern "C" int ht_xyzz_add(int curve, const uint8_t* p, const uint8_t* q, uint8_t* out, int n) {
+  if (curve == 0) return xyzz_add_op<CurveK256>(p, q, out, n);
+  return curve == 1 ? xyzz_add_op<CurveP256>(p, q, out, n) : xyzz_add_op<CurveP384>(p, q, out, n);
+}
+
 // ---- hash to curve: map_to_curve (count = 1) or the sum of two maps (count = 2), as the kernel does it (h2c_map.hpp) ----
 #include "h2c_map.hpp"
 template <class C>
