@@ -72,13 +72,13 @@ struct CurveOps {
     return 0;
   }
   static int ensure_gen_table(ecgpu_ctx* c) {
-    if (c->gen_table[C::ID]) return 0;
+    if (c->table[ECGPU_TAB_GEN][C::ID]) return 0;
     void* t = nullptr;
     HIPCHK(c, hipMalloc(&t, sizeof(typename C::Pt) * C::GEN_TABLE_PTS));
     hipLaunchKernelGGL((gen_table_kernel<C>), dim3(1), dim3(64), 0, c->stream, (typename C::Pt*)t);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(c->stream));     // later calls may run on another stream (ecgpu_set_stream)
-    c->gen_table[C::ID] = t;
+    c->table[ECGPU_TAB_GEN][C::ID] = t;
     return 0;
   }
   // fixed-base table T[j][d-1] = d 2^(8j) G (fixedbase.hpp), built once per context
@@ -88,7 +88,7 @@ struct CurveOps {
     if (window > c->fb_widest[C::ID]) c->fb_widest[C::ID] = window;
   }
   static int ensure_fb_table(ecgpu_ctx* c) {
-    if (c->fb_table[C::ID]) return 0;
+    if (c->table[ECGPU_TAB_FB8][C::ID]) return 0;
     const int total = fb::nwin<C>() * fb::ENTRIES;
     struct Tmp {                       // released on every exit path
       void* p = nullptr;
@@ -101,7 +101,7 @@ struct CurveOps {
     hipLaunchKernelGGL((fb::table_affine_kernel<C>), dim3((total + 255) / 256), dim3(256), 0, c->stream, (const Jac<C>*)tmp, (AffEntry<C>*)tab, total);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->fb_table[C::ID] = tab;
+    c->table[ECGPU_TAB_FB8][C::ID] = tab;
     ttab.p = nullptr;                  // owned by the context from here on
     fb_account(c, sizeof(AffEntry<C>) * total, fb::W);
     return 0;
@@ -117,7 +117,7 @@ struct CurveOps {
     int rc = ensure_fb_table(c);
     if (rc) return rc;
     if constexpr (WB > 20) {
-      if ((rc = ensure_fb_wide_table<20>(c, &c->fb20_table[C::ID]))) return rc;       // FB_NOMEM passes through
+      if ((rc = ensure_fb_wide_table<20>(c, &c->table[ECGPU_TAB_FB20][C::ID]))) return rc;       // FB_NOMEM passes through
     }
     const size_t total = (size_t)fb::nwin_wide<C, WB>() * fb::wide_entries<WB>();
     const size_t chunk = total < ((size_t)1 << 24) ? total : ((size_t)1 << 24);     // entries per pass: at most 1.5 GB (2.3 GB for p384) of scratch
@@ -149,10 +149,10 @@ struct CurveOps {
       hipLaunchKernelGGL((fb::table_scalars_kernel<C, WB>), dim3(ecgpu_grid_for(c, cnt, 8)), dim3(256), 0, c->stream, (u32*)ks, e0, cnt);
       if constexpr (WB > 20)
         hipLaunchKernelGGL((fb::mul_wide_kernel<C, 20, FB_BATCH, 4>), dim3(ecgpu_grid_for(c, cnt, 4)), dim3(256), 0, c->stream, (const u32*)ks,
-                           (const AffEntry<C>*)c->fb20_table[C::ID], (u32*)xy, FMT_AFFINE, (uint8_t*)nullptr, cnt, WaveSched{nullptr, 0, 0, 0, 0});
+                           (const AffEntry<C>*)c->table[ECGPU_TAB_FB20][C::ID], (u32*)xy, FMT_AFFINE, (uint8_t*)nullptr, cnt, WaveSched{nullptr, 0, 0, 0, 0});
       else
         hipLaunchKernelGGL((fb::mul_kernel<C, 16, 4>), dim3(ecgpu_grid_for(c, cnt, 4)), dim3(256), 0, c->stream, (const u32*)ks,
-                           (const AffEntry<C>*)c->fb_table[C::ID], (u32*)xy, FMT_AFFINE, (uint8_t*)nullptr, cnt);
+                           (const AffEntry<C>*)c->table[ECGPU_TAB_FB8][C::ID], (u32*)xy, FMT_AFFINE, (uint8_t*)nullptr, cnt);
       hipLaunchKernelGGL((fb::table_from_bytes_kernel<C>), dim3(ecgpu_grid_for(c, cnt, 8)), dim3(256), 0, c->stream, (const u32*)xy, tab + e0, cnt);
     }
     HIPCHK(c, hipGetLastError());
@@ -187,10 +187,10 @@ struct CurveOps {
       const int cap = (int)c->opt[ECGPU_OPT_FB_MAX_WINDOW];
       if (wb > cap) wb = cap;
       int rc;
-      if (wb >= 26) rc = mul_gen_wide<26>(c, &c->fb26_table[C::ID], sc, out, out_fmt, out_inf, n);
-      else if (wb >= 24) rc = mul_gen_wide<24>(c, &c->fb24_table[C::ID], sc, out, out_fmt, out_inf, n);
-      else if (wb >= 20) rc = mul_gen_wide<20>(c, &c->fb20_table[C::ID], sc, out, out_fmt, out_inf, n);
-      else if (wb >= 16) rc = mul_gen_wide<16>(c, &c->fb16_table[C::ID], sc, out, out_fmt, out_inf, n);
+      if (wb >= 26) rc = mul_gen_wide<26>(c, &c->table[ECGPU_TAB_FB26][C::ID], sc, out, out_fmt, out_inf, n);
+      else if (wb >= 24) rc = mul_gen_wide<24>(c, &c->table[ECGPU_TAB_FB24][C::ID], sc, out, out_fmt, out_inf, n);
+      else if (wb >= 20) rc = mul_gen_wide<20>(c, &c->table[ECGPU_TAB_FB20][C::ID], sc, out, out_fmt, out_inf, n);
+      else if (wb >= 16) rc = mul_gen_wide<16>(c, &c->table[ECGPU_TAB_FB16][C::ID], sc, out, out_fmt, out_inf, n);
       else break;
       if (rc != FB_NOMEM) return rc;
       wb = wb >= 26 ? 24 : wb >= 24 ? 20 : wb >= 20 ? 16 : 8;
@@ -199,20 +199,20 @@ struct CurveOps {
     int rc = ensure_fb_table(c);
     if (rc) return rc;
     hipLaunchKernelGGL((fb::mul_kernel<C, 16, 4>), dim3(ecgpu_grid_for(c, n, 4)), dim3(256), 0, c->stream, sc,
-                       (const AffEntry<C>*)c->fb_table[C::ID], out, out_fmt, out_inf, n);
+                       (const AffEntry<C>*)c->table[ECGPU_TAB_FB8][C::ID], out, out_fmt, out_inf, n);
     HIPCHK(c, hipGetLastError());
     return 1;
   }
   // k G for secret scalars: constant-time fixed-base kernel (fixedbase.hpp), one inversion per 8 results
   static int mul_gen_ct(ecgpu_ctx* c, const u32* sc, u32* out, int out_fmt, uint8_t* out_inf, size_t n) {
-    int rc = ensure_fb_wide_table<fb::CT_WB>(c, &c->fbct_table[C::ID]);
+    int rc = ensure_fb_wide_table<fb::CT_WB>(c, &c->table[ECGPU_TAB_FBCT][C::ID]);
     if (rc == FB_NOMEM) return ecgpu_set_err(c, ECGPU_ERR_RUNTIME, "hipMalloc failed (out of device memory) for the 5-bit generator table of the constant-time kernel");
     if (rc) return rc;
     if constexpr (C::ID == 0) {          // secp256k1: the kernel lives in the branch-free translation unit (ops_k256_ct.hip)
-      return ecgpuint_k256_mul_gen_ct(c, sc, c->fbct_table[C::ID], out, out_fmt, out_inf, n);
+      return ecgpuint_k256_mul_gen_ct(c, sc, c->table[ECGPU_TAB_FBCT][C::ID], out, out_fmt, out_inf, n);
     } else {
       constexpr int WAVES = FBCT_WAVES(C);
-      hipLaunchKernelGGL((fb::mul_ct_kernel<C, 8, WAVES>), dim3(ecgpu_grid_oversubscribed(c, n, WAVES, 8, FBCT_GRID_MULT)), dim3(256), 0, c->stream, sc, (const AffEntry<C>*)c->fbct_table[C::ID], out,
+      hipLaunchKernelGGL((fb::mul_ct_kernel<C, 8, WAVES>), dim3(ecgpu_grid_oversubscribed(c, n, WAVES, 8, FBCT_GRID_MULT)), dim3(256), 0, c->stream, sc, (const AffEntry<C>*)c->table[ECGPU_TAB_FBCT][C::ID], out,
                          out_fmt, out_inf, n);
       HIPCHK(c, hipGetLastError());
       return 0;
@@ -261,10 +261,10 @@ struct CurveOps {
       if (rc) return rc;
     }
     if constexpr (C::ID == 0) {            // secp256k1: in the branch-free translation unit (ops_k256_ct.hip)
-      return ecgpuint_k256_reference(c, sc, pts, pt_fmt, terms, c->gen_table[C::ID], out, out_fmt, out_inf, n);
+      return ecgpuint_k256_reference(c, sc, pts, pt_fmt, terms, c->table[ECGPU_TAB_GEN][C::ID], out, out_fmt, out_inf, n);
     } else {
       if (!pts) {
-        hipLaunchKernelGGL((mul_gen_ref_kernel<C>), dim3(g), dim3(256), 0, c->stream, sc, (const typename C::Pt*)c->gen_table[C::ID], out,
+        hipLaunchKernelGGL((mul_gen_ref_kernel<C>), dim3(g), dim3(256), 0, c->stream, sc, (const typename C::Pt*)c->table[ECGPU_TAB_GEN][C::ID], out,
                            out_fmt, out_inf, n);
       } else if (terms == 1) {
         hipLaunchKernelGGL((lincomb_ref_kernel<C, 1>), dim3(g), dim3(256), 0, c->stream, sc, pts, pt_fmt, out, out_fmt, out_inf, n);
@@ -275,12 +275,26 @@ struct CurveOps {
       return 0;
     }
   }
-  // the grow-only per-lane workspace of the variable-base kernels
-  static int tab_reserve(ecgpu_ctx* c, size_t need) {
-    if (need <= c->tab_ws_cap) return 0;
-    if (c->tab_ws) { HIPCHK(c, hipStreamSynchronize(c->stream)); HIPCHK(c, hipFree(c->tab_ws)); c->tab_ws = nullptr; c->tab_ws_cap = 0; }
-    HIPCHK(c, hipMalloc(&c->tab_ws, need));
-    c->tab_ws_cap = need;
+  // Carves the intermediate workspace (c->ecdsa_ws) into sub-buffers of 256-byte-aligned sizes.  `layout` asks for them with
+  // take<T>(bytes), in order; it runs twice: once to add the sizes up, then, the workspace reserved, to receive the pointers.
+  struct Carver {
+    char* base;
+    size_t total = 0;
+    template <class T>
+    T* take(size_t bytes) {
+      T* p = base ? (T*)(base + total) : nullptr;
+      total += (bytes + 255) & ~(size_t)255;
+      return p;
+    }
+  };
+  template <class Layout>
+  static int carve(ecgpu_ctx* c, Layout layout) {
+    Carver sizes{nullptr};
+    layout(sizes);
+    int rc = ecgpu_reserve(c, c->ecdsa_ws, sizes.total);
+    if (rc) return rc;
+    Carver ws{(char*)c->ecdsa_ws.p};
+    layout(ws);
     return 0;
   }
   // 3 .. 1024 terms per combination, throughput schedule (straus.hpp): groups of up to 16 terms share the doublings of one window
@@ -293,14 +307,14 @@ struct CurveOps {
     straus::plan(n, terms, resident_lanes(c, WAVES), &g, &gpc);
     const size_t items = n * (size_t)gpc, upp = (size_t)(straus::SLOTS / g);
     const unsigned grid = ecgpu_grid_for(c, (items + upp - 1) / upp, WAVES);
-    int rc = tab_reserve(c, (size_t)grid * 256 * sizeof(straus::LaneWs<C>));
+    int rc = ecgpu_reserve(c, c->tab_ws, (size_t)grid * 256 * sizeof(straus::LaneWs<C>));
     if (rc) return rc;
-    if ((rc = ecdsa_reserve(c, al256(items * 3 * C::NW * sizeof(u32))))) return rc;
-    u32* partial = (u32*)c->ecdsa_ws;
+    u32* partial;
+    if ((rc = carve(c, [&](Carver& ws) { partial = ws.template take<u32>(items * 3 * C::NW * sizeof(u32)); }))) return rc;
     unsigned long long* ctr = ecgpu_sched_counter(c);
     if (!ctr) return ECGPU_ERR_RUNTIME;
     hipLaunchKernelGGL((straus::lincomb_kernel<C, WAVES>), dim3(grid), dim3(256), 0, c->stream, sc, pts, pt_fmt, (int)terms, g, gpc, items,
-                       (straus::LaneWs<C>*)c->tab_ws, partial, WaveSched{ctr, (unsigned long long)items, grid * 4u, (unsigned)upp, 0u});
+                       (straus::LaneWs<C>*)c->tab_ws.p, partial, WaveSched{ctr, (unsigned long long)items, grid * 4u, (unsigned)upp, 0u});
     hipLaunchKernelGGL((straus::fold_kernel<C>), dim3(ecgpu_grid_for(c, (n + 15) / 16, 8)), dim3(256), 0, c->stream, (const u32*)partial, gpc, out, out_fmt, out_inf, n);
     HIPCHK(c, hipGetLastError());
     return 0;
@@ -351,11 +365,10 @@ struct CurveOps {
     const u32* xy = pts;
     const uint8_t* inf = nullptr;
     if (pt_fmt == FMT_PROJECTIVE) {
-      const size_t sz_p = al256(n * 2 * C::NB);
-      int rc = ecdsa_reserve(c, sz_p + al256(n));
+      u32* t;
+      uint8_t* ti;
+      int rc = carve(c, [&](Carver& ws) { t = ws.template take<u32>(n * 2 * C::NB); ti = ws.template take<uint8_t>(n); });
       if (rc) return rc;
-      u32* t = (u32*)c->ecdsa_ws;
-      uint8_t* ti = (uint8_t*)c->ecdsa_ws + sz_p;
       if ((rc = normalize(c, pts, t, ti, n))) return rc;
       xy = t; inf = ti;
     }
@@ -371,33 +384,40 @@ struct CurveOps {
     return 0;
   }
   static int from_bytes(ecgpu_ctx* c, const uint8_t* in, u32* out_xy, uint8_t* ok, size_t n) { return sec1_decode(c, in, 1 + C::NB, out_xy, ok, n); }
-  // ECDSA pipelines (ecdsa_kernels.hpp): the scalar multiplications run on the throughput kernels above
-  static int ecdsa_reserve(ecgpu_ctx* c, size_t need) {
-    if (need <= c->ecdsa_ws_cap) return 0;
-    if (c->ecdsa_ws) { HIPCHK(c, hipStreamSynchronize(c->stream)); HIPCHK(c, hipFree(c->ecdsa_ws)); c->ecdsa_ws = nullptr; c->ecdsa_ws_cap = 0; }
-    HIPCHK(c, hipMalloc(&c->ecdsa_ws, need));
-    c->ecdsa_ws_cap = need;
-    return 0;
+  // ECDSA / BIP340 verification and key recovery (ecdsa_kernels.hpp, schnorr_kernels.hpp) share one shape: a prep kernel writes the
+  // scalars u1, u2 (recovery and BIP340: a point `pt` as well), u1 G and u2 Q run on the throughput kernels above, a last kernel
+  // compares or combines the two products a and b.  The intermediates live in the workspace in the order of these members.
+  struct VerifyWs {
+    u32 *u1, *u2, *pt, *a, *b;
+    uint8_t *a_inf, *b_inf;
+  };
+  static int verify_ws(ecgpu_ctx* c, size_t n, bool with_pt, VerifyWs& w) {
+    return carve(c, [&](Carver& ws) {
+      w.u1 = ws.template take<u32>(n * C::NB);
+      w.u2 = ws.template take<u32>(n * C::NB);
+      w.pt = with_pt ? ws.template take<u32>(n * 2 * C::NB) : nullptr;
+      w.a = ws.template take<u32>(n * 2 * C::NB);
+      w.b = ws.template take<u32>(n * 2 * C::NB);
+      w.a_inf = ws.template take<uint8_t>(n);
+      w.b_inf = ws.template take<uint8_t>(n);
+    });
   }
-  static size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
-  static int ecdsa_verify(ecgpu_ctx* c, const u32* z, const u32* sig, const u32* q, uint8_t* ok, size_t n, unsigned flags) {
-    const size_t sz_s = al256(n * C::NB), sz_p = al256(n * 2 * C::NB), sz_f = al256(n);
-    int rc = ecdsa_reserve(c, 2 * sz_s + 2 * sz_p + 2 * sz_f);
-    if (rc) return rc;
-    char* p = (char*)c->ecdsa_ws;
-    u32* u1 = (u32*)p; p += sz_s;
-    u32* u2 = (u32*)p; p += sz_s;
-    u32* a = (u32*)p; p += sz_p;
-    u32* b = (u32*)p; p += sz_p;
-    uint8_t* a_inf = (uint8_t*)p; p += sz_f;
-    uint8_t* b_inf = (uint8_t*)p;
-    hipLaunchKernelGGL((ecdsa::verify_prep_kernel<C, 16>), dim3(ecgpu_grid_for(c, (n + 15) / 16, 4)), dim3(256), 0, c->stream, z, sig, q, u1, u2,
-                       ok, n, flags);
+  // a = u1 G, b = u2 Q (after the prep kernel's launch check)
+  static int verify_products(ecgpu_ctx* c, const VerifyWs& w, const u32* q, size_t n) {
     HIPCHK(c, hipGetLastError());
-    if ((rc = lincomb(c, u1, nullptr, FMT_AFFINE, 1, a, FMT_AFFINE, a_inf, n, 0))) return rc;
-    if ((rc = lincomb(c, u2, q, FMT_AFFINE, 1, b, FMT_AFFINE, b_inf, n, 0))) return rc;
-    hipLaunchKernelGGL((ecdsa::verify_check_kernel<C>), dim3(ecgpu_grid_for(c, n, 8)), dim3(256), 0, c->stream, (const u32*)a,
-                       (const uint8_t*)a_inf, (const u32*)b, (const uint8_t*)b_inf, sig, ok, n);
+    int rc = lincomb(c, w.u1, nullptr, FMT_AFFINE, 1, w.a, FMT_AFFINE, w.a_inf, n, 0);
+    if (rc) return rc;
+    return lincomb(c, w.u2, q, FMT_AFFINE, 1, w.b, FMT_AFFINE, w.b_inf, n, 0);
+  }
+  static int ecdsa_verify(ecgpu_ctx* c, const u32* z, const u32* sig, const u32* q, uint8_t* ok, size_t n, unsigned flags) {
+    VerifyWs w;
+    int rc = verify_ws(c, n, false, w);
+    if (rc) return rc;
+    hipLaunchKernelGGL((ecdsa::verify_prep_kernel<C, 16>), dim3(ecgpu_grid_for(c, (n + 15) / 16, 4)), dim3(256), 0, c->stream, z, sig, q, w.u1, w.u2,
+                       ok, n, flags);
+    if ((rc = verify_products(c, w, q, n))) return rc;
+    hipLaunchKernelGGL((ecdsa::verify_check_kernel<C>), dim3(ecgpu_grid_for(c, n, 8)), dim3(256), 0, c->stream, (const u32*)w.a,
+                       (const uint8_t*)w.a_inf, (const u32*)w.b, (const uint8_t*)w.b_inf, sig, ok, n);
     HIPCHK(c, hipGetLastError());
     return 0;
   }
@@ -407,24 +427,14 @@ struct CurveOps {
     return 0;
   }
   static int ecdsa_recover(ecgpu_ctx* c, const u32* z, const u32* sig, const uint8_t* recid, u32* out_xy, uint8_t* ok, size_t n, unsigned flags) {
-    const size_t sz_s = al256(n * C::NB), sz_p = al256(n * 2 * C::NB), sz_f = al256(n);
-    int rc = ecdsa_reserve(c, 2 * sz_s + 3 * sz_p + 2 * sz_f);
+    VerifyWs w;
+    int rc = verify_ws(c, n, true, w);
     if (rc) return rc;
-    char* p = (char*)c->ecdsa_ws;
-    u32* u1 = (u32*)p; p += sz_s;
-    u32* u2 = (u32*)p; p += sz_s;
-    u32* r_xy = (u32*)p; p += sz_p;
-    u32* a = (u32*)p; p += sz_p;
-    u32* b = (u32*)p; p += sz_p;
-    uint8_t* a_inf = (uint8_t*)p; p += sz_f;
-    uint8_t* b_inf = (uint8_t*)p;
-    hipLaunchKernelGGL((ecdsa::recover_prep_kernel<C, 16>), dim3(ecgpu_grid_for(c, (n + 15) / 16, 4)), dim3(256), 0, c->stream, z, sig, recid, r_xy, u1,
-                       u2, ok, n, flags);
-    HIPCHK(c, hipGetLastError());
-    if ((rc = lincomb(c, u1, nullptr, FMT_AFFINE, 1, a, FMT_AFFINE, a_inf, n, 0))) return rc;
-    if ((rc = lincomb(c, u2, r_xy, FMT_AFFINE, 1, b, FMT_AFFINE, b_inf, n, 0))) return rc;
-    hipLaunchKernelGGL((ecdsa::recover_finish_kernel<C, 16>), dim3(ecgpu_grid_for(c, (n + 15) / 16, 8)), dim3(256), 0, c->stream, (const u32*)a,
-                       (const uint8_t*)a_inf, (const u32*)b, (const uint8_t*)b_inf, out_xy, ok, n);
+    hipLaunchKernelGGL((ecdsa::recover_prep_kernel<C, 16>), dim3(ecgpu_grid_for(c, (n + 15) / 16, 4)), dim3(256), 0, c->stream, z, sig, recid, w.pt, w.u1,
+                       w.u2, ok, n, flags);
+    if ((rc = verify_products(c, w, w.pt, n))) return rc;
+    hipLaunchKernelGGL((ecdsa::recover_finish_kernel<C, 16>), dim3(ecgpu_grid_for(c, (n + 15) / 16, 8)), dim3(256), 0, c->stream, (const u32*)w.a,
+                       (const uint8_t*)w.a_inf, (const u32*)w.b, (const uint8_t*)w.b_inf, out_xy, ok, n);
     HIPCHK(c, hipGetLastError());
     return 0;
   }
@@ -433,23 +443,13 @@ struct CurveOps {
     if constexpr (C::ID != 0) {
       return ecgpu_set_err(c, ECGPU_ERR_UNSUPPORTED, "ecgpu_schnorr_verify_batch: BIP340 is defined over secp256k1 only");
     } else {
-      const size_t sz_s = al256(n * C::NB), sz_p = al256(n * 2 * C::NB), sz_f = al256(n);
-      int rc = ecdsa_reserve(c, 2 * sz_s + 3 * sz_p + 2 * sz_f);
+      VerifyWs w;
+      int rc = verify_ws(c, n, true, w);
       if (rc) return rc;
-      char* p = (char*)c->ecdsa_ws;
-      u32* u1 = (u32*)p; p += sz_s;
-      u32* u2 = (u32*)p; p += sz_s;
-      u32* key = (u32*)p; p += sz_p;
-      u32* a = (u32*)p; p += sz_p;
-      u32* b = (u32*)p; p += sz_p;
-      uint8_t* a_inf = (uint8_t*)p; p += sz_f;
-      uint8_t* b_inf = (uint8_t*)p;
-      hipLaunchKernelGGL((schnorr::verify_prep_kernel<0>), dim3(ecgpu_grid_for(c, n, 8)), dim3(256), 0, c->stream, px, sig, e, key, u1, u2, ok, n);
-      HIPCHK(c, hipGetLastError());
-      if ((rc = lincomb(c, u1, nullptr, FMT_AFFINE, 1, a, FMT_AFFINE, a_inf, n, 0))) return rc;
-      if ((rc = lincomb(c, u2, key, FMT_AFFINE, 1, b, FMT_AFFINE, b_inf, n, 0))) return rc;
-      hipLaunchKernelGGL((schnorr::verify_check_kernel<16>), dim3(ecgpu_grid_for(c, (n + 15) / 16, 8)), dim3(256), 0, c->stream, (const u32*)a,
-                         (const uint8_t*)a_inf, (const u32*)b, (const uint8_t*)b_inf, sig, ok, n);
+      hipLaunchKernelGGL((schnorr::verify_prep_kernel<0>), dim3(ecgpu_grid_for(c, n, 8)), dim3(256), 0, c->stream, px, sig, e, w.pt, w.u1, w.u2, ok, n);
+      if ((rc = verify_products(c, w, w.pt, n))) return rc;
+      hipLaunchKernelGGL((schnorr::verify_check_kernel<16>), dim3(ecgpu_grid_for(c, (n + 15) / 16, 8)), dim3(256), 0, c->stream, (const u32*)w.a,
+                         (const uint8_t*)w.a_inf, (const u32*)w.b, (const uint8_t*)w.b_inf, sig, ok, n);
       HIPCHK(c, hipGetLastError());
       return 0;
     }
@@ -457,11 +457,9 @@ struct CurveOps {
   // ECDH (ecdh_kernels.hpp): input checks, the secret-scalar multiplication (constant-time kernel where the curve has
   // one, the reference schedule otherwise), x of the product
   static int ecdh(ecgpu_ctx* c, const u32* d, const u32* q, u32* shared_x, uint8_t* ok, size_t n) {
-    const size_t sz_p = al256(n * 2 * C::NB);
-    int rc = ecdsa_reserve(c, 2 * sz_p);
+    u32 *prod, *q_sane;
+    int rc = carve(c, [&](Carver& ws) { prod = ws.template take<u32>(n * 2 * C::NB); q_sane = ws.template take<u32>(n * 2 * C::NB); });
     if (rc) return rc;
-    u32* prod = (u32*)c->ecdsa_ws;
-    u32* q_sane = (u32*)((char*)c->ecdsa_ws + sz_p);
     // the products are secrets of the same rank as the shared values handed back: they do not stay in the workspace, whichever way
     // this function is left (the constant-time kernels clear what they park in the table workspace themselves)
     struct ProdWipe {
@@ -477,11 +475,10 @@ struct CurveOps {
   }
   static int ecdsa_sign(ecgpu_ctx* c, const u32* d, const u32* k, const u32* z, u32* sig, uint8_t* recid, uint8_t* ok, size_t n,
                         unsigned flags) {
-    const size_t sz_p = al256(n * 2 * C::NB), sz_f = al256(n);
-    int rc = ecdsa_reserve(c, sz_p + sz_f);
+    u32* r_xy;
+    uint8_t* r_inf;
+    int rc = carve(c, [&](Carver& ws) { r_xy = ws.template take<u32>(n * 2 * C::NB); r_inf = ws.template take<uint8_t>(n); });
     if (rc) return rc;
-    u32* r_xy = (u32*)c->ecdsa_ws;
-    uint8_t* r_inf = (uint8_t*)c->ecdsa_ws + sz_p;
     // The nonce is secret: k G runs on the constant-time fixed-base kernel (every table entry read, one masked addition per window,
     // no digit-dependent branch or address) - or, with ECGPU_EXACT_REFERENCE, on the reference's own mul_by_generator
     // schedule, which is constant-time as well - unless the caller declares the scalars public.

@@ -1,6 +1,14 @@
 // C ABI of libecgpu.so (include/ecgpu.h): context, staging of host buffers, dispatch to the
 // per-curve kernel launchers (ops_*.hip).  Host side of the boundary; all arithmetic happens in
 // the gfx950 kernels.  There is deliberately no CPU code path in this library.
+//
+// Every batched entry point is three parts: its argument checks, ONE list of its caller buffers (CallArg: pointer, direction,
+// bytes per element, secret or not) and one launch lambda, the only place that casts to the launcher's pointer types.
+// run_batch does the rest from the list.  Device memory: the pointers pass through.  Host memory: the buffers are staged in the
+// context's grow-only device slots - whole, the i-th input of the list in slot {0, 1, 4}[i] and the j-th output in {2, 3, 5}[j]
+// (an absent optional buffer keeps its place in the count), or, for the calls that name a pass size and from PIPE_MIN elements
+// on, in chunks through the pipeline (host_pipe.hpp), list entry a of pipeline slot s in slot 6 + 6 s + a.  What the list marks
+// secret is cleared from its slots (and from the pipeline's bounce buffers) before the call returns, whichever way it ends.
 #include <string.h>
 #include <condition_variable>
 #include <thread>
@@ -10,50 +18,30 @@
 #include "host_pipe.hpp"
 
 static int stage_reserve(ecgpu_ctx* c, int slot, size_t bytes) {
-  if (bytes <= c->stage_cap[slot]) return 0;
-  if (c->stage[slot]) {
-    HIPCHK(c, hipStreamSynchronize(c->stream));          // work queued on the old buffer
-    HIPCHK(c, hipFree(c->stage[slot]));
-  }
-  c->stage[slot] = nullptr;
-  c->stage_cap[slot] = 0;
-  size_t cap = bytes + bytes / 4 + 256;
-  HIPCHK(c, hipMalloc(&c->stage[slot], cap));
-  c->stage_cap[slot] = cap;
+  DevBuf& b = c->stage[slot];
+  if (bytes <= b.cap) return 0;
+  int rc = ecgpu_reserve(c, b, bytes + bytes / 4 + 256);
+  if (rc) return rc;
   // recycled memory keeps its old contents: a slot starts out zero, its slack included (waited for: the pipeline's own streams use it next)
-  HIPCHK(c, hipMemsetAsync(c->stage[slot], 0, cap, c->stream));
+  HIPCHK(c, hipMemsetAsync(b.p, 0, b.cap, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return 0;
 }
 
-// A device view of one caller buffer: either the pointer itself or a staged copy.
-struct Buf {
-  void* host_out = nullptr;
-  void* dev = nullptr;
-  size_t bytes = 0;
-};
-static int buf_in(ecgpu_ctx* c, Buf& b, int slot, const void* p, size_t bytes, int mem) {
-  b.bytes = bytes;
-  if (!p || bytes == 0) { b.dev = nullptr; return 0; }
-  if (mem == ECGPU_MEM_DEVICE) { b.dev = const_cast<void*>(p); return 0; }
+// The device view of one caller buffer: the pointer itself, or staging slot `slot` (an input is copied into it).
+static int stage_arg(ecgpu_ctx* c, int slot, const void* p, size_t bytes, bool is_out, int mem, void** dev) {
+  *dev = nullptr;
+  if (!p || bytes == 0) return 0;
+  if (mem == ECGPU_MEM_DEVICE) { *dev = const_cast<void*>(p); return 0; }
   int rc = stage_reserve(c, slot, bytes);
   if (rc) return rc;
-  b.dev = c->stage[slot];
-  HIPCHK(c, hipMemcpyAsync(b.dev, p, bytes, hipMemcpyHostToDevice, c->stream));
+  *dev = c->stage[slot].p;
+  if (!is_out) HIPCHK(c, hipMemcpyAsync(*dev, p, bytes, hipMemcpyHostToDevice, c->stream));
   return 0;
 }
-static int buf_out(ecgpu_ctx* c, Buf& b, int slot, void* p, size_t bytes, int mem) {
-  b.bytes = bytes;
-  if (!p || bytes == 0) { b.dev = nullptr; return 0; }
-  if (mem == ECGPU_MEM_DEVICE) { b.dev = p; return 0; }
-  int rc = stage_reserve(c, slot, bytes);
-  if (rc) return rc;
-  b.dev = c->stage[slot];
-  b.host_out = p;
-  return 0;
-}
-static int buf_finish(ecgpu_ctx* c, Buf& b) {
-  if (b.host_out && b.dev) HIPCHK(c, hipMemcpyAsync(b.host_out, b.dev, b.bytes, hipMemcpyDeviceToHost, c->stream));
+// a staged output goes back to the caller's buffer
+static int unstage_out(ecgpu_ctx* c, void* p, const void* dev, size_t bytes, int mem) {
+  if (dev && mem != ECGPU_MEM_DEVICE) HIPCHK(c, hipMemcpyAsync(p, dev, bytes, hipMemcpyDeviceToHost, c->stream));
   return 0;
 }
 static int finish_host(ecgpu_ctx* c, int mem) {
@@ -70,14 +58,98 @@ static constexpr size_t PIPE_MIN = (size_t)1 << 21;
 // one multi-scalar multiplication from host memory: sums of MSM_PIPE_MIN terms and more are cut into parts of MSM_PIPE_PART terms
 // (a part is one slab of either window width: msm_kernels.hpp Geo<CB>::SLAB_TERMS >= 2^23)
 static constexpr size_t MSM_PIPE_MIN = (size_t)1 << 22, MSM_PIPE_PART = (size_t)1 << 23;
-using PipeArg = hostpipe::Arg;
 extern "C" int ecgpu_host_chunk_schedule(size_t n, size_t pass_units, size_t* sizes, size_t cap);
-template <class Launch>
-static int host_pipeline(ecgpu_ctx* c, const PipeArg* args, int nargs, size_t n, size_t pass, bool secret, Launch launch) {
-  std::vector<size_t> sizes((size_t)ecgpu_host_chunk_schedule(n, pass, nullptr, 0));
-  (void)ecgpu_host_chunk_schedule(n, pass, sizes.data(), sizes.size());
-  return hostpipe::run(c, args, nargs, sizes, secret, [&](int slot, size_t bytes) { return stage_reserve(c, slot, bytes); },
-                       [&](void** d, size_t cnt, size_t) { return launch(d, cnt); });
+
+// One caller buffer of a batched call.
+struct CallArg {
+  const void* ptr;     // host or device memory, as the call's `mem` says
+  bool is_out;
+  size_t unit;         // bytes per batch element
+  bool secret;         // its staged copy does not outlive the call
+  bool optional;       // NULL means absent
+};
+enum : unsigned { ARG_SECRET = 1, ARG_OPTIONAL = 2 };
+static constexpr CallArg arg_in(const void* p, size_t unit, unsigned flags = 0) { return {p, false, unit, (flags & ARG_SECRET) != 0, (flags & ARG_OPTIONAL) != 0}; }
+static constexpr CallArg arg_out(void* p, size_t unit, unsigned flags = 0) { return {p, true, unit, (flags & ARG_SECRET) != 0, (flags & ARG_OPTIONAL) != 0}; }
+
+// The slot rule (include/ecgpu.h, ecgpu_debug_workspace).  Staged whole, list entry k goes by its direction and by how many
+// entries of that direction precede it, present or absent; in the pipeline by its position alone (hostpipe::stage_index).
+static constexpr int WHOLE_IN_SLOT[3] = {0, 1, 4}, WHOLE_OUT_SLOT[3] = {2, 3, 5};
+static constexpr int whole_slot(const CallArg* args, int k) {
+  int before = 0;
+  for (int i = 0; i < k; i++) before += args[i].is_out == args[k].is_out;
+  return (args[k].is_out ? WHOLE_OUT_SLOT : WHOLE_IN_SLOT)[before];
+}
+namespace slot_rule_check {
+// the shape of ecgpu_ecdsa_sign_batch, the longest list: d, k, z in; sig, recid, ok out
+constexpr CallArg sign[6] = {arg_in(nullptr, 32), arg_in(nullptr, 32), arg_in(nullptr, 32), arg_out(nullptr, 64), arg_out(nullptr, 1), arg_out(nullptr, 1)};
+static_assert(whole_slot(sign, 0) == 0 && whole_slot(sign, 1) == 1 && whole_slot(sign, 2) == 4, "inputs of a whole batch: slots 0, 1, 4");
+static_assert(whole_slot(sign, 3) == 2 && whole_slot(sign, 4) == 3 && whole_slot(sign, 5) == 5, "outputs of a whole batch: slots 2, 3, 5");
+// ecgpu_ecdsa_recover_batch: z, sig, recid in; keys, ok out
+constexpr CallArg recover[5] = {arg_in(nullptr, 32), arg_in(nullptr, 64), arg_in(nullptr, 1), arg_out(nullptr, 64), arg_out(nullptr, 1)};
+static_assert(whole_slot(recover, 2) == 4 && whole_slot(recover, 3) == 2 && whole_slot(recover, 4) == 3, "recover: recovery ids in 4, keys in 2, ok in 3");
+static_assert(ecgpu_ctx::PIPE_STAGE0 == 6 && ecgpu_ctx::PIPE_MAXARGS == 6 && ecgpu_ctx::PIPE_NSLOT == 3, "6 whole-batch slots, then 3 pipeline slots of 6 arguments");
+static_assert(hostpipe::stage_index(0, 0) == 6 && hostpipe::stage_index(1, 2) == 14 && hostpipe::stage_index(2, 5) == 23, "argument a of pipeline slot s: 6 + 6 s + a");
+static_assert(hostpipe::stage_index(ecgpu_ctx::PIPE_NSLOT - 1, ecgpu_ctx::PIPE_MAXARGS - 1) == ecgpu_ctx::NSTAGE - 1, "the last staging slot");
+}  // namespace slot_rule_check
+
+// Staged copies of secret scalars do not outlive the call (the reference zeroizes its secrets): the guard clears the
+// bytes this call staged in its slots on EVERY exit path, the error returns included, and waits for the clearing.
+struct SecretWipe {
+  ecgpu_ctx* c;
+  static constexpr int CAP = 3 * ecgpu_ctx::PIPE_NSLOT + 3;
+  int slot[CAP];
+  size_t bytes[CAP];
+  int cnt = 0;
+  explicit SecretWipe(ecgpu_ctx* ctx) : c(ctx) {}
+  void arm(int s, size_t b) { if (cnt < CAP) { slot[cnt] = s; bytes[cnt] = b; cnt++; } }
+  // argument `a` of every pipeline slot, whole capacity (the chunk sizes vary)
+  void arm_pipeline(int a) { for (int sl = 0; sl < ecgpu_ctx::PIPE_NSLOT; sl++) arm(hostpipe::stage_index(sl, a), (size_t)-1); }
+  ~SecretWipe() {
+    if (!cnt) return;
+    for (int i = 0; i < cnt; i++) {
+      const DevBuf& s = c->stage[slot[i]];
+      const size_t b = bytes[i] < s.cap ? bytes[i] : s.cap;
+      if (s.p && b) (void)hipMemsetAsync(s.p, 0, b, c->stream);
+    }
+    (void)hipStreamSynchronize(c->stream);
+    (void)hipGetLastError();
+  }
+};
+
+// One batched call over the buffers of `args`: launch(dev, cnt) enqueues the kernels for cnt elements on c->stream, dev[k] being
+// the device view of args[k] (nullptr for an absent one).  pass_units is the curve's ops->pass_units for the call's dominant
+// kernel; 0: the call never streams in chunks.
+template <size_t N, class Launch>
+static int run_batch(ecgpu_ctx* c, int mem, size_t n, const CallArg (&args)[N], size_t pass_units, Launch launch) {
+  static_assert(N <= (size_t)ecgpu_ctx::PIPE_MAXARGS, "a pipeline slot stages PIPE_MAXARGS arguments");
+  for (const CallArg& a : args)
+    if (!a.ptr && !a.optional) return ecgpu_set_err(c, ECGPU_ERR_ARG, "null argument");
+  const bool host = mem == ECGPU_MEM_HOST;
+  SecretWipe wipe(c);
+  if (host && pass_units && n >= PIPE_MIN) {
+    hostpipe::Arg pa[N];
+    bool secret = false;
+    for (size_t k = 0; k < N; k++) {
+      pa[k] = {args[k].is_out ? nullptr : args[k].ptr, args[k].is_out ? const_cast<void*>(args[k].ptr) : nullptr, args[k].unit};
+      if (args[k].secret) { wipe.arm_pipeline((int)k); secret = true; }
+    }
+    std::vector<size_t> sizes((size_t)ecgpu_host_chunk_schedule(n, pass_units, nullptr, 0));
+    (void)ecgpu_host_chunk_schedule(n, pass_units, sizes.data(), sizes.size());
+    return hostpipe::run(c, pa, (int)N, sizes, secret, [&](int slot, size_t bytes) { return stage_reserve(c, slot, bytes); },
+                         [&](void** d, size_t cnt, size_t) { return launch(d, cnt); });
+  }
+  if (host)
+    for (size_t k = 0; k < N; k++)
+      if (args[k].secret) wipe.arm(whole_slot(args, (int)k), n * args[k].unit);
+  void* dev[N];
+  int rc;
+  for (size_t k = 0; k < N; k++)
+    if ((rc = stage_arg(c, whole_slot(args, (int)k), args[k].ptr, n * args[k].unit, args[k].is_out, mem, &dev[k]))) return rc;
+  if ((rc = launch(dev, n))) return rc;
+  for (size_t k = 0; k < N; k++)
+    if (args[k].is_out && (rc = unstage_out(c, const_cast<void*>(args[k].ptr), dev[k], n * args[k].unit, mem))) return rc;
+  return finish_host(c, mem);
 }
 
 static const ecgpu_curve_ops* ops_for(int curve) {
@@ -137,9 +209,9 @@ void ecgpu_destroy(ecgpu_ctx* c) {
   (void)hipSetDevice(c->device);
   (void)hipStreamSynchronize(c->stream);
   for (int i = 0; i < ecgpu_ctx::NSTAGE; i++)
-    if (c->stage[i]) {                       // staging slots may have held secret scalars: clear before release
-      (void)hipMemset(c->stage[i], 0, c->stage_cap[i]);
-      (void)hipFree(c->stage[i]);
+    if (c->stage[i].p) {                     // staging slots may have held secret scalars: clear before release
+      (void)hipMemset(c->stage[i].p, 0, c->stage[i].cap);
+      (void)hipFree(c->stage[i].p);
     }
   for (int i = 0; i < ecgpu_ctx::PIPE_NSLOT; i++) {
     if (c->ev_kernel[i]) (void)hipEventDestroy(c->ev_kernel[i]);
@@ -153,16 +225,11 @@ void ecgpu_destroy(ecgpu_ctx* c) {
     }
   if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
   if (c->up_stream) (void)hipStreamDestroy(c->up_stream);
-  for (int i = 0; i < 3; i++) if (c->gen_table[i]) (void)hipFree(c->gen_table[i]);
-  for (int i = 0; i < 3; i++) if (c->fb_table[i]) (void)hipFree(c->fb_table[i]);
-  for (int i = 0; i < 3; i++) if (c->fb16_table[i]) (void)hipFree(c->fb16_table[i]);
-  for (int i = 0; i < 3; i++) if (c->fb20_table[i]) (void)hipFree(c->fb20_table[i]);
-  for (int i = 0; i < 3; i++) if (c->fb24_table[i]) (void)hipFree(c->fb24_table[i]);
-  for (int i = 0; i < 3; i++) if (c->fbct_table[i]) (void)hipFree(c->fbct_table[i]);
-  for (int i = 0; i < 3; i++) if (c->fb26_table[i]) (void)hipFree(c->fb26_table[i]);
-  if (c->msm_ws) (void)hipFree(c->msm_ws);
-  if (c->tab_ws) (void)hipFree(c->tab_ws);
-  if (c->ecdsa_ws) (void)hipFree(c->ecdsa_ws);
+  for (auto& kind : c->table)
+    for (void* t : kind)
+      if (t) (void)hipFree(t);
+  for (DevBuf* b : {&c->msm_ws, &c->tab_ws, &c->ecdsa_ws})
+    if (b->p) (void)hipFree(b->p);
   if (c->sched_ctr) (void)hipFree(c->sched_ctr);
   if (c->ev0) (void)hipEventDestroy(c->ev0);
   if (c->ev1) (void)hipEventDestroy(c->ev1);
@@ -263,13 +330,14 @@ int ecgpu_debug_workspace(ecgpu_ctx* c, int which, void* host_copy, size_t cap, 
   if (!c || !bytes) return ecgpu_set_err(c, ECGPU_ERR_ARG, "null argument");
   std::lock_guard<std::mutex> lk(c->mu);
   HIPCHK(c, hipSetDevice(c->device));
-  void* p = nullptr;
-  size_t sz = 0;
-  if (which == 0) { p = c->tab_ws; sz = c->tab_ws_cap; }
-  else if (which == 1) { p = c->ecdsa_ws; sz = c->ecdsa_ws_cap; }
-  else if (which == 2) { p = c->msm_ws; sz = c->msm_ws_cap; }
-  else if (which >= 16 && which < 16 + ecgpu_ctx::NSTAGE) { p = c->stage[which - 16]; sz = c->stage_cap[which - 16]; }
+  const DevBuf* ws;
+  if (which == 0) ws = &c->tab_ws;
+  else if (which == 1) ws = &c->ecdsa_ws;
+  else if (which == 2) ws = &c->msm_ws;
+  else if (which >= 16 && which < 16 + ecgpu_ctx::NSTAGE) ws = &c->stage[which - 16];
   else return ecgpu_set_err(c, ECGPU_ERR_ARG, "ecgpu_debug_workspace: unknown workspace %d", which);
+  void* p = ws->p;
+  const size_t sz = ws->cap;
   *bytes = sz;
   if (host_copy && p && sz && cap) {
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -319,48 +387,48 @@ int ecgpu_field_op_batch(ecgpu_ctx* c, int curve, int op, const uint8_t* a, cons
   if (binary && !b) return ecgpu_set_err(c, ECGPU_ERR_ARG, "binary field op needs b");
   if (n == 0) return ECGPU_OK;
   ENTER(c, curve);
-  Buf ba, bb, bo;
-  int rc;
-  if ((rc = buf_in(c, ba, 0, a, n * nb, mem))) return rc;
-  if ((rc = buf_in(c, bb, 1, binary ? b : nullptr, n * nb, mem))) return rc;
-  if ((rc = buf_out(c, bo, 2, out, n * nb, mem))) return rc;
-  if ((rc = ops->field_op(c, op, (const uint32_t*)ba.dev, (const uint32_t*)bb.dev, (uint32_t*)bo.dev, n))) return rc;
-  if ((rc = buf_finish(c, bo))) return rc;
-  return finish_host(c, mem);
+  const CallArg args[] = {arg_in(a, nb), arg_in(binary ? b : nullptr, nb, ARG_OPTIONAL), arg_out(out, nb)};
+  return run_batch(c, mem, n, args, 0, [&](void** d, size_t cnt) {
+    return ops->field_op(c, op, (const uint32_t*)d[0], (const uint32_t*)d[1], (uint32_t*)d[2], cnt);
+  });
 }
 
-static bool scalar_op_binary(int op) { return op == ECGPU_SC_MUL || op == ECGPU_SC_ADD || op == ECGPU_SC_SUB; }
-static int scalar_op_impl(ecgpu_ctx* c, int curve, int op, const uint8_t* a, const uint8_t* b, uint8_t* out, uint8_t* ok, size_t n, int mem);
-static int scalar_reduce_impl(ecgpu_ctx* c, int curve, const uint8_t* in, size_t in_bytes, uint8_t* out, size_t n, int mem, unsigned flags);
+// scalar field: operands are usually secrets, so their staged copies and the staged results are cleared on every exit path
 int ecgpu_scalar_op_batch(ecgpu_ctx* c, int curve, int op, const uint8_t* a, const uint8_t* b, uint8_t* out, uint8_t* ok, size_t n, int mem) {
   if (!c || !a || !out) return ecgpu_set_err(c, ECGPU_ERR_ARG, "null argument");
   if (op < ECGPU_SC_MUL || op > ECGPU_SC_SQRT) return ecgpu_set_err(c, ECGPU_ERR_ARG, "unknown scalar op %d", op);
-  if (scalar_op_binary(op) && !b) return ecgpu_set_err(c, ECGPU_ERR_ARG, "binary scalar op needs b");
+  const bool binary = (op == ECGPU_SC_MUL || op == ECGPU_SC_ADD || op == ECGPU_SC_SUB);
+  if (binary && !b) return ecgpu_set_err(c, ECGPU_ERR_ARG, "binary scalar op needs b");
   if (n == 0) return ECGPU_OK;
-  return scalar_op_impl(c, curve, op, a, b, out, ok, n, mem);
+  ENTER(c, curve);
+  const CallArg args[] = {arg_in(a, nb, ARG_SECRET), arg_in(binary ? b : nullptr, nb, binary ? ARG_SECRET : ARG_OPTIONAL),
+                          arg_out(out, nb, ARG_SECRET), arg_out(ok, 1, ARG_SECRET | ARG_OPTIONAL)};
+  return run_batch(c, mem, n, args, 0, [&](void** d, size_t cnt) {
+    return ops->scalar_op(c, op, (const uint32_t*)d[0], (const uint32_t*)d[1], (uint32_t*)d[2], (uint8_t*)d[3], cnt);
+  });
 }
 int ecgpu_scalar_reduce_batch(ecgpu_ctx* c, int curve, const uint8_t* in, size_t in_bytes, uint8_t* out, size_t n, int mem, unsigned flags) {
   if (!c || !in || !out) return ecgpu_set_err(c, ECGPU_ERR_ARG, "null argument");
-  const size_t nb = ecgpu_field_bytes(curve);
-  if (!nb) return ecgpu_set_err(c, ECGPU_ERR_UNSUPPORTED, "curve %d not supported", curve);
-  if (in_bytes < 1 || in_bytes > 2 * nb) return ecgpu_set_err(c, ECGPU_ERR_ARG, "in_bytes %zu outside 1 .. %zu", in_bytes, 2 * nb);
+  const size_t width = ecgpu_field_bytes(curve);
+  if (!width) return ecgpu_set_err(c, ECGPU_ERR_UNSUPPORTED, "curve %d not supported", curve);
+  if (in_bytes < 1 || in_bytes > 2 * width) return ecgpu_set_err(c, ECGPU_ERR_ARG, "in_bytes %zu outside 1 .. %zu", in_bytes, 2 * width);
   if (flags & ~(unsigned)ECGPU_REDUCE_NONZERO) return ecgpu_set_err(c, ECGPU_ERR_ARG, "unknown reduce flags 0x%x", flags);
   if (n == 0) return ECGPU_OK;
-  return scalar_reduce_impl(c, curve, in, in_bytes, out, n, mem, flags);
+  ENTER(c, curve);
+  const CallArg args[] = {arg_in(in, in_bytes, ARG_SECRET), arg_out(out, nb, ARG_SECRET)};
+  return run_batch(c, mem, n, args, 0, [&](void** d, size_t cnt) {
+    return ops->scalar_reduce(c, (const uint8_t*)d[0], in_bytes, (uint32_t*)d[1], cnt, flags);
+  });
 }
 
 static int point_op(ecgpu_ctx* c, int curve, int op, const uint8_t* p, const uint8_t* q, int q_coords, uint8_t* out, size_t n, int mem) {
   if (!c || !p || !out || (q_coords && !q)) return ecgpu_set_err(c, ECGPU_ERR_ARG, "null argument");
   if (n == 0) return ECGPU_OK;
   ENTER(c, curve);
-  Buf bp, bq, bo;
-  int rc;
-  if ((rc = buf_in(c, bp, 0, p, n * 3 * nb, mem))) return rc;
-  if ((rc = buf_in(c, bq, 1, q, n * q_coords * nb, mem))) return rc;
-  if ((rc = buf_out(c, bo, 2, out, n * 3 * nb, mem))) return rc;
-  if ((rc = ops->point_op(c, op, (const uint32_t*)bp.dev, (const uint32_t*)bq.dev, (uint32_t*)bo.dev, n))) return rc;
-  if ((rc = buf_finish(c, bo))) return rc;
-  return finish_host(c, mem);
+  const CallArg args[] = {arg_in(p, 3 * nb), arg_in(q, q_coords * nb, q_coords ? 0 : ARG_OPTIONAL), arg_out(out, 3 * nb)};
+  return run_batch(c, mem, n, args, 0, [&](void** d, size_t cnt) {
+    return ops->point_op(c, op, (const uint32_t*)d[0], (const uint32_t*)d[1], (uint32_t*)d[2], cnt);
+  });
 }
 int ecgpu_point_add_batch(ecgpu_ctx* c, int curve, const uint8_t* p, const uint8_t* q, uint8_t* out, size_t n, int mem) {
   return point_op(c, curve, 0, p, q, 3, out, n, mem);
@@ -376,82 +444,20 @@ int ecgpu_point_eq_batch(ecgpu_ctx* c, int curve, const uint8_t* p, const uint8_
   if (!c || !p || !q || !eq) return ecgpu_set_err(c, ECGPU_ERR_ARG, "null argument");
   if (n == 0) return ECGPU_OK;
   ENTER(c, curve);
-  Buf bp, bq, bo;
-  int rc;
-  if ((rc = buf_in(c, bp, 0, p, n * 3 * nb, mem))) return rc;
-  if ((rc = buf_in(c, bq, 1, q, n * 3 * nb, mem))) return rc;
-  if ((rc = buf_out(c, bo, 2, eq, n, mem))) return rc;
-  if ((rc = ops->point_eq(c, (const uint32_t*)bp.dev, (const uint32_t*)bq.dev, (uint8_t*)bo.dev, n))) return rc;
-  if ((rc = buf_finish(c, bo))) return rc;
-  return finish_host(c, mem);
+  const CallArg args[] = {arg_in(p, 3 * nb), arg_in(q, 3 * nb), arg_out(eq, 1)};
+  return run_batch(c, mem, n, args, 0, [&](void** d, size_t cnt) {
+    return ops->point_eq(c, (const uint32_t*)d[0], (const uint32_t*)d[1], (uint8_t*)d[2], cnt);
+  });
 }
 
 int ecgpu_batch_normalize(ecgpu_ctx* c, int curve, const uint8_t* p, uint8_t* out_xy, uint8_t* out_inf, size_t n, int mem) {
   if (!c || !p || !out_xy) return ecgpu_set_err(c, ECGPU_ERR_ARG, "null argument");
   if (n == 0) return ECGPU_OK;
   ENTER(c, curve);
-  Buf bp, bo, bi;
-  int rc;
-  if ((rc = buf_in(c, bp, 0, p, n * 3 * nb, mem))) return rc;
-  if ((rc = buf_out(c, bo, 2, out_xy, n * 2 * nb, mem))) return rc;
-  if ((rc = buf_out(c, bi, 3, out_inf, n, mem))) return rc;
-  if ((rc = ops->normalize(c, (const uint32_t*)bp.dev, (uint32_t*)bo.dev, (uint8_t*)bi.dev, n))) return rc;
-  if ((rc = buf_finish(c, bo))) return rc;
-  if ((rc = buf_finish(c, bi))) return rc;
-  return finish_host(c, mem);
-}
-
-// Staged copies of secret scalars do not outlive the call (the reference zeroizes its secrets): the guard clears the
-// bytes this call staged in its slots on EVERY exit path, the error returns included, and waits for the clearing.
-struct SecretWipe {
-  ecgpu_ctx* c;
-  static constexpr int CAP = 3 * ecgpu_ctx::PIPE_NSLOT + 3;
-  int slot[CAP];
-  size_t bytes[CAP];
-  int cnt = 0;
-  explicit SecretWipe(ecgpu_ctx* ctx) : c(ctx) {}
-  void arm(int s, size_t b) { if (cnt < CAP) { slot[cnt] = s; bytes[cnt] = b; cnt++; } }
-  // argument `a` of every pipeline slot, whole capacity (the chunk sizes vary)
-  void arm_pipeline(int a) { for (int sl = 0; sl < ecgpu_ctx::PIPE_NSLOT; sl++) arm(hostpipe::stage_index(sl, a), (size_t)-1); }
-  ~SecretWipe() {
-    if (!cnt) return;
-    for (int i = 0; i < cnt; i++) {
-      const size_t b = bytes[i] < c->stage_cap[slot[i]] ? bytes[i] : c->stage_cap[slot[i]];
-      if (c->stage[slot[i]] && b) (void)hipMemsetAsync(c->stage[slot[i]], 0, b, c->stream);
-    }
-    (void)hipStreamSynchronize(c->stream);
-    (void)hipGetLastError();
-  }
-};
-
-// scalar field: operands are usually secrets, so their staged copies and the staged results are cleared on every exit path
-static int scalar_op_impl(ecgpu_ctx* c, int curve, int op, const uint8_t* a, const uint8_t* b, uint8_t* out, uint8_t* ok, size_t n, int mem) {
-  ENTER(c, curve);
-  const bool binary = scalar_op_binary(op);
-  SecretWipe wipe(c);
-  if (mem == ECGPU_MEM_HOST) { wipe.arm(0, n * nb); if (binary) wipe.arm(1, n * nb); wipe.arm(2, n * nb); wipe.arm(3, n); }
-  Buf ba, bb, bo, bk;
-  int rc;
-  if ((rc = buf_in(c, ba, 0, a, n * nb, mem))) return rc;
-  if ((rc = buf_in(c, bb, 1, binary ? b : nullptr, n * nb, mem))) return rc;
-  if ((rc = buf_out(c, bo, 2, out, n * nb, mem))) return rc;
-  if ((rc = buf_out(c, bk, 3, ok, n, mem))) return rc;
-  if ((rc = ops->scalar_op(c, op, (const uint32_t*)ba.dev, (const uint32_t*)bb.dev, (uint32_t*)bo.dev, (uint8_t*)bk.dev, n))) return rc;
-  if ((rc = buf_finish(c, bo))) return rc;
-  if ((rc = buf_finish(c, bk))) return rc;
-  return finish_host(c, mem);
-}
-static int scalar_reduce_impl(ecgpu_ctx* c, int curve, const uint8_t* in, size_t in_bytes, uint8_t* out, size_t n, int mem, unsigned flags) {
-  ENTER(c, curve);
-  SecretWipe wipe(c);
-  if (mem == ECGPU_MEM_HOST) { wipe.arm(0, n * in_bytes); wipe.arm(2, n * nb); }
-  Buf bi, bo;
-  int rc;
-  if ((rc = buf_in(c, bi, 0, in, n * in_bytes, mem))) return rc;
-  if ((rc = buf_out(c, bo, 2, out, n * nb, mem))) return rc;
-  if ((rc = ops->scalar_reduce(c, (const uint8_t*)bi.dev, in_bytes, (uint32_t*)bo.dev, n, flags))) return rc;
-  if ((rc = buf_finish(c, bo))) return rc;
-  return finish_host(c, mem);
+  const CallArg args[] = {arg_in(p, 3 * nb), arg_out(out_xy, 2 * nb), arg_out(out_inf, 1, ARG_OPTIONAL)};
+  return run_batch(c, mem, n, args, 0, [&](void** d, size_t cnt) {
+    return ops->normalize(c, (const uint32_t*)d[0], (uint32_t*)d[1], (uint8_t*)d[2], cnt);
+  });
 }
 
 static int lincomb_impl(ecgpu_ctx* c, int curve, const uint8_t* scalars, const uint8_t* points, int pt_fmt, size_t terms, uint8_t* out, int out_fmt,
@@ -463,38 +469,19 @@ static int lincomb_impl(ecgpu_ctx* c, int curve, const uint8_t* scalars, const u
   if (n == 0) return ECGPU_OK;
   ENTER(c, curve);
   const size_t pin = (pt_fmt == ECGPU_PT_PROJECTIVE ? 3 : 2) * nb, pout = (out_fmt == ECGPU_PT_PROJECTIVE ? 3 : 2) * nb;
-  // the reference schedule is the one meant for secret scalars: their staged copies do not outlive the call
-  const bool secret = (flags & (ECGPU_EXACT_REFERENCE | ECGPU_SECRET_SCALARS)) != 0;
-  SecretWipe wipe(c);
-  if (mem == ECGPU_MEM_HOST && n >= PIPE_MIN) {
-    if (secret) { wipe.arm_pipeline(0); if (flags & ECGPU_SECRET_SCALARS) wipe.arm_pipeline(2); }    // the scalars; for a secret scalar the product is a secret too
-    const PipeArg args[5] = {{scalars, nullptr, terms * nb}, {points, nullptr, points ? terms * pin : 0}, {nullptr, out, pout},
-                             {nullptr, out_fmt == ECGPU_PT_AFFINE ? out_inf : nullptr, 1}, {nullptr, scalar_ok, 1}};
-    int rc = host_pipeline(c, args, 5, n, ops->pass_units(c, points != nullptr, terms, flags), secret, [&](void** d, size_t cnt) {
-      if (d[4]) {
-        int r2 = ops->validate_scalars(c, (const uint32_t*)d[0], (uint8_t*)d[4], cnt, terms);
-        if (r2) return r2;
-      }
-      return ops->lincomb(c, (const uint32_t*)d[0], (const uint32_t*)d[1], pt_fmt, terms, (uint32_t*)d[2], out_fmt, (uint8_t*)d[3], cnt, flags);
-    });
-    return rc;
-  }
-  Buf bs, bp, bo, bi, bk;
-  int rc;
-  if (secret && mem == ECGPU_MEM_HOST) { wipe.arm(0, n * terms * nb); if (flags & ECGPU_SECRET_SCALARS) wipe.arm(2, n * pout); }
-  if ((rc = buf_in(c, bs, 0, scalars, n * terms * nb, mem))) return rc;
-  if ((rc = buf_in(c, bp, 1, points, n * terms * pin, mem))) return rc;
-  if ((rc = buf_out(c, bo, 2, out, n * pout, mem))) return rc;
-  if ((rc = buf_out(c, bi, 3, out_fmt == ECGPU_PT_AFFINE ? out_inf : nullptr, n, mem))) return rc;
-  if ((rc = buf_out(c, bk, 5, scalar_ok, n, mem))) return rc;
-  if (bk.dev && (rc = ops->validate_scalars(c, (const uint32_t*)bs.dev, (uint8_t*)bk.dev, n, terms))) return rc;
-  if ((rc = ops->lincomb(c, (const uint32_t*)bs.dev, (const uint32_t*)bp.dev, pt_fmt, terms, (uint32_t*)bo.dev, out_fmt,
-                         (uint8_t*)bi.dev, n, flags)))
-    return rc;
-  if ((rc = buf_finish(c, bo))) return rc;
-  if ((rc = buf_finish(c, bi))) return rc;
-  if ((rc = buf_finish(c, bk))) return rc;
-  return finish_host(c, mem);
+  // the reference schedule is the one meant for secret scalars: their staged copies do not outlive the call; for a secret scalar
+  // the product is a secret too
+  const unsigned sc_secret = (flags & (ECGPU_EXACT_REFERENCE | ECGPU_SECRET_SCALARS)) ? ARG_SECRET : 0;
+  const unsigned out_secret = (flags & ECGPU_SECRET_SCALARS) ? ARG_SECRET : 0;
+  const CallArg args[] = {arg_in(scalars, terms * nb, sc_secret), arg_in(points, terms * pin, ARG_OPTIONAL), arg_out(out, pout, out_secret),
+                          arg_out(out_fmt == ECGPU_PT_AFFINE ? out_inf : nullptr, 1, ARG_OPTIONAL), arg_out(scalar_ok, 1, ARG_OPTIONAL)};
+  return run_batch(c, mem, n, args, ops->pass_units(c, points != nullptr, terms, flags), [&](void** d, size_t cnt) {
+    if (d[4]) {
+      int rc = ops->validate_scalars(c, (const uint32_t*)d[0], (uint8_t*)d[4], cnt, terms);
+      if (rc) return rc;
+    }
+    return ops->lincomb(c, (const uint32_t*)d[0], (const uint32_t*)d[1], pt_fmt, terms, (uint32_t*)d[2], out_fmt, (uint8_t*)d[3], cnt, flags);
+  });
 }
 
 int ecgpu_lincomb_batch(ecgpu_ctx* c, int curve, const uint8_t* scalars, const uint8_t* points, int pt_fmt, size_t terms,
@@ -518,7 +505,7 @@ int ecgpu_mul_batch_checked(ecgpu_ctx* c, int curve, const uint8_t* scalars, con
 }
 
 // `mem` is where the inputs live, `out_mem` where the one result point goes (the device group sums host-resident slices into
-// device-resident partial points: group.hip)
+// device-resident partial points: group.hip).  The scalars go to staging slot 0, the points to 1, the result to 2.
 static int msm_impl(ecgpu_ctx* c, int curve, const uint8_t* scalars, const uint8_t* points, int pt_fmt, size_t n, uint8_t* out, int out_fmt,
                     int mem, int out_mem) {
   if (!c || !out || (n && (!scalars || !points))) return ecgpu_set_err(c, ECGPU_ERR_ARG, "null argument");
@@ -526,7 +513,7 @@ static int msm_impl(ecgpu_ctx* c, int curve, const uint8_t* scalars, const uint8
     return ecgpu_set_err(c, ECGPU_ERR_ARG, "bad point format");
   ENTER(c, curve);
   const size_t pin = (pt_fmt == ECGPU_PT_PROJECTIVE ? 3 : 2) * nb, pout = (out_fmt == ECGPU_PT_PROJECTIVE ? 3 : 2) * nb;
-  Buf bs, bp, bo;
+  void *ds, *dp, *dout;
   int rc;
   if (n == 0) {                              // the empty sum is the identity: affine zeros, projective (0 : 1 : 0)
     if (out_mem == ECGPU_MEM_HOST) {
@@ -546,8 +533,8 @@ static int msm_impl(ecgpu_ctx* c, int curve, const uint8_t* scalars, const uint8
     const size_t parts = sizes.size();
     if ((rc = stage_reserve(c, 3, parts * 3 * nb))) return rc;
     if ((rc = stage_reserve(c, 4, parts * nb))) return rc;
-    uint8_t* partial = (uint8_t*)c->stage[3];
-    const PipeArg args[2] = {{scalars, nullptr, nb}, {points, nullptr, pin}};
+    uint8_t* partial = (uint8_t*)c->stage[3].p;
+    const hostpipe::Arg args[2] = {{scalars, nullptr, nb}, {points, nullptr, pin}};
     rc = hostpipe::run(c, args, 2, sizes, false, [&](int slot, size_t bytes) { return stage_reserve(c, slot, bytes); },
                        [&](void** d, size_t cnt, size_t ci) {
                          return ops->msm(c, (const uint32_t*)d[0], (const uint32_t*)d[1], pt_fmt, cnt, (uint32_t*)(partial + ci * 3 * nb), ECGPU_PT_PROJECTIVE);
@@ -555,17 +542,17 @@ static int msm_impl(ecgpu_ctx* c, int curve, const uint8_t* scalars, const uint8
     if (rc) return rc;
     std::vector<uint8_t> ones(parts * nb, 0);
     for (size_t i = 0; i < parts; i++) ones[i * nb + nb - 1] = 1;
-    HIPCHK(c, hipMemcpyAsync(c->stage[4], ones.data(), parts * nb, hipMemcpyHostToDevice, c->stream));
-    if ((rc = buf_out(c, bo, 2, out, pout, out_mem))) return rc;
-    if ((rc = ops->msm(c, (const uint32_t*)c->stage[4], (const uint32_t*)partial, ECGPU_PT_PROJECTIVE, parts, (uint32_t*)bo.dev, out_fmt))) return rc;
-    if ((rc = buf_finish(c, bo))) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->stage[4].p, ones.data(), parts * nb, hipMemcpyHostToDevice, c->stream));
+    if ((rc = stage_arg(c, 2, out, pout, true, out_mem, &dout))) return rc;
+    if ((rc = ops->msm(c, (const uint32_t*)c->stage[4].p, (const uint32_t*)partial, ECGPU_PT_PROJECTIVE, parts, (uint32_t*)dout, out_fmt))) return rc;
+    if ((rc = unstage_out(c, out, dout, pout, out_mem))) return rc;
     return finish_host(c, ECGPU_MEM_HOST);   // `ones` lives until the stream has been synchronised here
   }
-  if ((rc = buf_in(c, bs, 0, scalars, n * nb, mem))) return rc;
-  if ((rc = buf_in(c, bp, 1, points, n * pin, mem))) return rc;
-  if ((rc = buf_out(c, bo, 2, out, pout, out_mem))) return rc;
-  if ((rc = ops->msm(c, (const uint32_t*)bs.dev, (const uint32_t*)bp.dev, pt_fmt, n, (uint32_t*)bo.dev, out_fmt))) return rc;
-  if ((rc = buf_finish(c, bo))) return rc;
+  if ((rc = stage_arg(c, 0, scalars, n * nb, false, mem, &ds))) return rc;
+  if ((rc = stage_arg(c, 1, points, n * pin, false, mem, &dp))) return rc;
+  if ((rc = stage_arg(c, 2, out, pout, true, out_mem, &dout))) return rc;
+  if ((rc = ops->msm(c, (const uint32_t*)ds, (const uint32_t*)dp, pt_fmt, n, (uint32_t*)dout, out_fmt))) return rc;
+  if ((rc = unstage_out(c, out, dout, pout, out_mem))) return rc;
   return finish_host(c, (mem == ECGPU_MEM_HOST || out_mem == ECGPU_MEM_HOST) ? ECGPU_MEM_HOST : ECGPU_MEM_DEVICE);    // staged inputs must have left the host buffers
 }
 int ecgpu_msm(ecgpu_ctx* c, int curve, const uint8_t* scalars, const uint8_t* points, int pt_fmt, size_t n, uint8_t* out, int out_fmt,
@@ -579,40 +566,24 @@ int ecgpu_validate_scalars(ecgpu_ctx* c, int curve, const uint8_t* scalars, uint
   if (!c || !scalars || !ok) return ecgpu_set_err(c, ECGPU_ERR_ARG, "null argument");
   if (n == 0) return ECGPU_OK;
   ENTER(c, curve);
-  Buf bs, bo;
-  int rc;
-  if ((rc = buf_in(c, bs, 0, scalars, n * nb, mem))) return rc;
-  if ((rc = buf_out(c, bo, 2, ok, n, mem))) return rc;
-  if ((rc = ops->validate_scalars(c, (const uint32_t*)bs.dev, (uint8_t*)bo.dev, n, 1))) return rc;
-  if ((rc = buf_finish(c, bo))) return rc;
-  return finish_host(c, mem);
+  const CallArg args[] = {arg_in(scalars, nb), arg_out(ok, 1)};
+  return run_batch(c, mem, n, args, 0, [&](void** d, size_t cnt) { return ops->validate_scalars(c, (const uint32_t*)d[0], (uint8_t*)d[1], cnt, 1); });
 }
 int ecgpu_validate_points(ecgpu_ctx* c, int curve, const uint8_t* xy, uint8_t* ok, size_t n, int mem) {
   if (!c || !xy || !ok) return ecgpu_set_err(c, ECGPU_ERR_ARG, "null argument");
   if (n == 0) return ECGPU_OK;
   ENTER(c, curve);
-  Buf bs, bo;
-  int rc;
-  if ((rc = buf_in(c, bs, 0, xy, n * 2 * nb, mem))) return rc;
-  if ((rc = buf_out(c, bo, 2, ok, n, mem))) return rc;
-  if ((rc = ops->validate_points(c, (const uint32_t*)bs.dev, (uint8_t*)bo.dev, n))) return rc;
-  if ((rc = buf_finish(c, bo))) return rc;
-  return finish_host(c, mem);
+  const CallArg args[] = {arg_in(xy, 2 * nb), arg_out(ok, 1)};
+  return run_batch(c, mem, n, args, 0, [&](void** d, size_t cnt) { return ops->validate_points(c, (const uint32_t*)d[0], (uint8_t*)d[1], cnt); });
 }
 int ecgpu_decompress_batch(ecgpu_ctx* c, int curve, const uint8_t* x, const uint8_t* y_is_odd, uint8_t* out_xy, uint8_t* ok, size_t n, int mem) {
   if (!c || !x || !y_is_odd || !out_xy || !ok) return ecgpu_set_err(c, ECGPU_ERR_ARG, "null argument");
   if (n == 0) return ECGPU_OK;
   ENTER(c, curve);
-  Buf bx, by, bo, bk;
-  int rc;
-  if ((rc = buf_in(c, bx, 0, x, n * nb, mem))) return rc;
-  if ((rc = buf_in(c, by, 1, y_is_odd, n, mem))) return rc;
-  if ((rc = buf_out(c, bo, 2, out_xy, n * 2 * nb, mem))) return rc;
-  if ((rc = buf_out(c, bk, 3, ok, n, mem))) return rc;
-  if ((rc = ops->decompress(c, (const uint32_t*)bx.dev, (const uint8_t*)by.dev, (uint32_t*)bo.dev, (uint8_t*)bk.dev, n))) return rc;
-  if ((rc = buf_finish(c, bo))) return rc;
-  if ((rc = buf_finish(c, bk))) return rc;
-  return finish_host(c, mem);
+  const CallArg args[] = {arg_in(x, nb), arg_in(y_is_odd, 1), arg_out(out_xy, 2 * nb), arg_out(ok, 1)};
+  return run_batch(c, mem, n, args, 0, [&](void** d, size_t cnt) {
+    return ops->decompress(c, (const uint32_t*)d[0], (const uint8_t*)d[1], (uint32_t*)d[2], (uint8_t*)d[3], cnt);
+  });
 }
 
 int ecgpu_to_bytes_batch(ecgpu_ctx* c, int curve, const uint8_t* points, int pt_fmt, uint8_t* out, size_t n, int mem) {
@@ -620,27 +591,15 @@ int ecgpu_to_bytes_batch(ecgpu_ctx* c, int curve, const uint8_t* points, int pt_
   if (pt_fmt != ECGPU_PT_AFFINE && pt_fmt != ECGPU_PT_PROJECTIVE) return ecgpu_set_err(c, ECGPU_ERR_ARG, "bad point format");
   if (n == 0) return ECGPU_OK;
   ENTER(c, curve);
-  Buf bp, bo;
-  int rc;
-  if ((rc = buf_in(c, bp, 0, points, n * (pt_fmt == ECGPU_PT_PROJECTIVE ? 3 : 2) * nb, mem))) return rc;
-  if ((rc = buf_out(c, bo, 2, out, n * (nb + 1), mem))) return rc;
-  if ((rc = ops->to_bytes(c, (const uint32_t*)bp.dev, pt_fmt, (uint8_t*)bo.dev, n))) return rc;
-  if ((rc = buf_finish(c, bo))) return rc;
-  return finish_host(c, mem);
+  const CallArg args[] = {arg_in(points, (pt_fmt == ECGPU_PT_PROJECTIVE ? 3 : 2) * nb), arg_out(out, nb + 1)};
+  return run_batch(c, mem, n, args, 0, [&](void** d, size_t cnt) { return ops->to_bytes(c, (const uint32_t*)d[0], pt_fmt, (uint8_t*)d[1], cnt); });
 }
 int ecgpu_from_bytes_batch(ecgpu_ctx* c, int curve, const uint8_t* in, uint8_t* out_xy, uint8_t* ok, size_t n, int mem) {
   if (!c || !in || !out_xy || !ok) return ecgpu_set_err(c, ECGPU_ERR_ARG, "null argument");
   if (n == 0) return ECGPU_OK;
   ENTER(c, curve);
-  Buf bi, bo, bk;
-  int rc;
-  if ((rc = buf_in(c, bi, 0, in, n * (nb + 1), mem))) return rc;
-  if ((rc = buf_out(c, bo, 2, out_xy, n * 2 * nb, mem))) return rc;
-  if ((rc = buf_out(c, bk, 3, ok, n, mem))) return rc;
-  if ((rc = ops->from_bytes(c, (const uint8_t*)bi.dev, (uint32_t*)bo.dev, (uint8_t*)bk.dev, n))) return rc;
-  if ((rc = buf_finish(c, bo))) return rc;
-  if ((rc = buf_finish(c, bk))) return rc;
-  return finish_host(c, mem);
+  const CallArg args[] = {arg_in(in, nb + 1), arg_out(out_xy, 2 * nb), arg_out(ok, 1)};
+  return run_batch(c, mem, n, args, 0, [&](void** d, size_t cnt) { return ops->from_bytes(c, (const uint8_t*)d[0], (uint32_t*)d[1], (uint8_t*)d[2], cnt); });
 }
 
 int ecgpu_sec1_encode_batch(ecgpu_ctx* c, int curve, const uint8_t* points, int pt_fmt, int compress, uint8_t* out, size_t n, int mem) {
@@ -648,14 +607,10 @@ int ecgpu_sec1_encode_batch(ecgpu_ctx* c, int curve, const uint8_t* points, int 
   if (pt_fmt != ECGPU_PT_AFFINE && pt_fmt != ECGPU_PT_PROJECTIVE) return ecgpu_set_err(c, ECGPU_ERR_ARG, "bad point format");
   if (n == 0) return ECGPU_OK;
   ENTER(c, curve);
-  const size_t rec = 1 + (compress ? 1 : 2) * nb;
-  Buf bp, bo;
-  int rc;
-  if ((rc = buf_in(c, bp, 0, points, n * (pt_fmt == ECGPU_PT_PROJECTIVE ? 3 : 2) * nb, mem))) return rc;
-  if ((rc = buf_out(c, bo, 2, out, n * rec, mem))) return rc;
-  if ((rc = ops->sec1_encode(c, (const uint32_t*)bp.dev, pt_fmt, compress ? 1 : 0, (uint8_t*)bo.dev, n))) return rc;
-  if ((rc = buf_finish(c, bo))) return rc;
-  return finish_host(c, mem);
+  const CallArg args[] = {arg_in(points, (pt_fmt == ECGPU_PT_PROJECTIVE ? 3 : 2) * nb), arg_out(out, 1 + (compress ? 1 : 2) * nb)};
+  return run_batch(c, mem, n, args, 0, [&](void** d, size_t cnt) {
+    return ops->sec1_encode(c, (const uint32_t*)d[0], pt_fmt, compress ? 1 : 0, (uint8_t*)d[1], cnt);
+  });
 }
 int ecgpu_sec1_decode_batch(ecgpu_ctx* c, int curve, const uint8_t* in, size_t record_bytes, uint8_t* out_xy, uint8_t* ok, size_t n, int mem) {
   if (!c || !in || !out_xy || !ok) return ecgpu_set_err(c, ECGPU_ERR_ARG, "null argument");
@@ -663,15 +618,10 @@ int ecgpu_sec1_decode_batch(ecgpu_ctx* c, int curve, const uint8_t* in, size_t r
   ENTER(c, curve);
   if (record_bytes != 1 + nb && record_bytes != 1 + 2 * nb)
     return ecgpu_set_err(c, ECGPU_ERR_ARG, "ecgpu_sec1_decode_batch: record_bytes must be %zu (compressed) or %zu (uncompressed)", 1 + nb, 1 + 2 * nb);
-  Buf bi, bo, bk;
-  int rc;
-  if ((rc = buf_in(c, bi, 0, in, n * record_bytes, mem))) return rc;
-  if ((rc = buf_out(c, bo, 2, out_xy, n * 2 * nb, mem))) return rc;
-  if ((rc = buf_out(c, bk, 3, ok, n, mem))) return rc;
-  if ((rc = ops->sec1_decode(c, (const uint8_t*)bi.dev, record_bytes, (uint32_t*)bo.dev, (uint8_t*)bk.dev, n))) return rc;
-  if ((rc = buf_finish(c, bo))) return rc;
-  if ((rc = buf_finish(c, bk))) return rc;
-  return finish_host(c, mem);
+  const CallArg args[] = {arg_in(in, record_bytes), arg_out(out_xy, 2 * nb), arg_out(ok, 1)};
+  return run_batch(c, mem, n, args, 0, [&](void** d, size_t cnt) {
+    return ops->sec1_decode(c, (const uint8_t*)d[0], record_bytes, (uint32_t*)d[1], (uint8_t*)d[2], cnt);
+  });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -680,141 +630,66 @@ int ecgpu_ecdsa_verify_batch(ecgpu_ctx* c, int curve, const uint8_t* prehash, co
   if (!c || !prehash || !sig_rs || !pubkeys_xy || !ok) return ecgpu_set_err(c, ECGPU_ERR_ARG, "null argument");
   if (n == 0) return ECGPU_OK;
   ENTER(c, curve);
-  if (mem == ECGPU_MEM_HOST && n >= PIPE_MIN) {
-    const PipeArg args[4] = {{prehash, nullptr, nb}, {sig_rs, nullptr, 2 * nb}, {pubkeys_xy, nullptr, 2 * nb}, {nullptr, ok, 1}};
-    return host_pipeline(c, args, 4, n, ops->pass_units(c, 1, 1, 0), false, [&](void** d, size_t cnt) {
-      return ops->ecdsa_verify(c, (const uint32_t*)d[0], (const uint32_t*)d[1], (const uint32_t*)d[2], (uint8_t*)d[3], cnt, flags);
-    });
-  }
-  Buf bz, bs, bq, bo;
-  int rc;
-  if ((rc = buf_in(c, bz, 0, prehash, n * nb, mem))) return rc;
-  if ((rc = buf_in(c, bs, 1, sig_rs, n * 2 * nb, mem))) return rc;
-  if ((rc = buf_in(c, bq, 4, pubkeys_xy, n * 2 * nb, mem))) return rc;
-  if ((rc = buf_out(c, bo, 2, ok, n, mem))) return rc;
-  if ((rc = ops->ecdsa_verify(c, (const uint32_t*)bz.dev, (const uint32_t*)bs.dev, (const uint32_t*)bq.dev, (uint8_t*)bo.dev, n, flags))) return rc;
-  if ((rc = buf_finish(c, bo))) return rc;
-  return finish_host(c, mem);
+  const CallArg args[] = {arg_in(prehash, nb), arg_in(sig_rs, 2 * nb), arg_in(pubkeys_xy, 2 * nb), arg_out(ok, 1)};
+  return run_batch(c, mem, n, args, ops->pass_units(c, 1, 1, 0), [&](void** d, size_t cnt) {
+    return ops->ecdsa_verify(c, (const uint32_t*)d[0], (const uint32_t*)d[1], (const uint32_t*)d[2], (uint8_t*)d[3], cnt, flags);
+  });
 }
 int ecgpu_map_to_curve_batch(ecgpu_ctx* c, int curve, const uint8_t* u, int count, uint8_t* out_xy, uint8_t* out_inf, size_t n, int mem) {
   if (!c || !u || !out_xy) return ecgpu_set_err(c, ECGPU_ERR_ARG, "null argument");
   if (count != 1 && count != 2) return ecgpu_set_err(c, ECGPU_ERR_ARG, "count must be 1 (map_to_curve) or 2 (hash_to_curve: Q0 + Q1)");
   if (n == 0) return ECGPU_OK;
   ENTER(c, curve);
-  Buf bu, bo, bi;
-  int rc;
-  if ((rc = buf_in(c, bu, 0, u, n * count * nb, mem))) return rc;
-  if ((rc = buf_out(c, bo, 2, out_xy, n * 2 * nb, mem))) return rc;
-  if ((rc = buf_out(c, bi, 3, out_inf, n, mem))) return rc;
-  if ((rc = ops->h2c_map(c, (const uint32_t*)bu.dev, count, (uint32_t*)bo.dev, (uint8_t*)bi.dev, n))) return rc;
-  if ((rc = buf_finish(c, bo))) return rc;
-  if ((rc = buf_finish(c, bi))) return rc;
-  return finish_host(c, mem);
+  const CallArg args[] = {arg_in(u, count * nb), arg_out(out_xy, 2 * nb), arg_out(out_inf, 1, ARG_OPTIONAL)};
+  return run_batch(c, mem, n, args, 0, [&](void** d, size_t cnt) {
+    return ops->h2c_map(c, (const uint32_t*)d[0], count, (uint32_t*)d[1], (uint8_t*)d[2], cnt);
+  });
 }
 int ecgpu_ecdsa_recover_batch(ecgpu_ctx* c, int curve, const uint8_t* prehash, const uint8_t* sig_rs, const uint8_t* recovery_id,
                               uint8_t* pubkeys_xy, uint8_t* ok, size_t n, int mem, unsigned flags) {
   if (!c || !prehash || !sig_rs || !recovery_id || !pubkeys_xy || !ok) return ecgpu_set_err(c, ECGPU_ERR_ARG, "null argument");
   if (n == 0) return ECGPU_OK;
   ENTER(c, curve);
-  if (mem == ECGPU_MEM_HOST && n >= PIPE_MIN) {
-    const PipeArg args[5] = {{prehash, nullptr, nb}, {sig_rs, nullptr, 2 * nb}, {recovery_id, nullptr, 1}, {nullptr, pubkeys_xy, 2 * nb}, {nullptr, ok, 1}};
-    return host_pipeline(c, args, 5, n, ops->pass_units(c, 1, 1, 0), false, [&](void** d, size_t cnt) {
-      return ops->ecdsa_recover(c, (const uint32_t*)d[0], (const uint32_t*)d[1], (const uint8_t*)d[2], (uint32_t*)d[3], (uint8_t*)d[4], cnt, flags);
-    });
-  }
-  Buf bz, bs, br, bq, bo;
-  int rc;
-  if ((rc = buf_in(c, bz, 0, prehash, n * nb, mem))) return rc;
-  if ((rc = buf_in(c, bs, 1, sig_rs, n * 2 * nb, mem))) return rc;
-  if ((rc = buf_in(c, br, 4, recovery_id, n, mem))) return rc;
-  if ((rc = buf_out(c, bq, 2, pubkeys_xy, n * 2 * nb, mem))) return rc;
-  if ((rc = buf_out(c, bo, 3, ok, n, mem))) return rc;
-  if ((rc = ops->ecdsa_recover(c, (const uint32_t*)bz.dev, (const uint32_t*)bs.dev, (const uint8_t*)br.dev, (uint32_t*)bq.dev, (uint8_t*)bo.dev, n,
-                               flags)))
-    return rc;
-  if ((rc = buf_finish(c, bq))) return rc;
-  if ((rc = buf_finish(c, bo))) return rc;
-  return finish_host(c, mem);
+  const CallArg args[] = {arg_in(prehash, nb), arg_in(sig_rs, 2 * nb), arg_in(recovery_id, 1), arg_out(pubkeys_xy, 2 * nb), arg_out(ok, 1)};
+  return run_batch(c, mem, n, args, ops->pass_units(c, 1, 1, 0), [&](void** d, size_t cnt) {
+    return ops->ecdsa_recover(c, (const uint32_t*)d[0], (const uint32_t*)d[1], (const uint8_t*)d[2], (uint32_t*)d[3], (uint8_t*)d[4], cnt, flags);
+  });
 }
 int ecgpu_schnorr_verify_batch(ecgpu_ctx* c, int curve, const uint8_t* pubkeys_x, const uint8_t* sig_rs, const uint8_t* challenges, uint8_t* ok,
                                size_t n, int mem) {
   if (!c || !pubkeys_x || !sig_rs || !challenges || !ok) return ecgpu_set_err(c, ECGPU_ERR_ARG, "null argument");
   if (n == 0) return ECGPU_OK;
   ENTER(c, curve);
-  if (mem == ECGPU_MEM_HOST && n >= PIPE_MIN) {
-    const PipeArg args[4] = {{pubkeys_x, nullptr, nb}, {sig_rs, nullptr, 2 * nb}, {challenges, nullptr, nb}, {nullptr, ok, 1}};
-    return host_pipeline(c, args, 4, n, ops->pass_units(c, 1, 1, 0), false, [&](void** d, size_t cnt) {
-      return ops->schnorr_verify(c, (const uint32_t*)d[0], (const uint32_t*)d[1], (const uint32_t*)d[2], (uint8_t*)d[3], cnt);
-    });
-  }
-  Buf bx, bs, be, bo;
-  int rc;
-  if ((rc = buf_in(c, bx, 0, pubkeys_x, n * nb, mem))) return rc;
-  if ((rc = buf_in(c, bs, 1, sig_rs, n * 2 * nb, mem))) return rc;
-  if ((rc = buf_in(c, be, 4, challenges, n * nb, mem))) return rc;
-  if ((rc = buf_out(c, bo, 2, ok, n, mem))) return rc;
-  if ((rc = ops->schnorr_verify(c, (const uint32_t*)bx.dev, (const uint32_t*)bs.dev, (const uint32_t*)be.dev, (uint8_t*)bo.dev, n))) return rc;
-  if ((rc = buf_finish(c, bo))) return rc;
-  return finish_host(c, mem);
+  const CallArg args[] = {arg_in(pubkeys_x, nb), arg_in(sig_rs, 2 * nb), arg_in(challenges, nb), arg_out(ok, 1)};
+  return run_batch(c, mem, n, args, ops->pass_units(c, 1, 1, 0), [&](void** d, size_t cnt) {
+    return ops->schnorr_verify(c, (const uint32_t*)d[0], (const uint32_t*)d[1], (const uint32_t*)d[2], (uint8_t*)d[3], cnt);
+  });
 }
+// staged secret keys and nonces are cleared on every exit path (the signature is public)
 int ecgpu_ecdsa_sign_batch(ecgpu_ctx* c, int curve, const uint8_t* secret_d, const uint8_t* nonce_k, const uint8_t* prehash, uint8_t* sig_rs,
                            uint8_t* recovery_id, uint8_t* ok, size_t n, int mem, unsigned flags) {
   if (!c || !secret_d || !nonce_k || !prehash || !sig_rs || !ok) return ecgpu_set_err(c, ECGPU_ERR_ARG, "null argument");
   if (n == 0) return ECGPU_OK;
   ENTER(c, curve);
-  SecretWipe wipe(c);                        // staged secret keys and nonces are cleared on every exit path
-  if (mem == ECGPU_MEM_HOST && n >= PIPE_MIN) {
-    wipe.arm_pipeline(0); wipe.arm_pipeline(1);          // secret keys, nonces
-    const PipeArg args[6] = {{secret_d, nullptr, nb}, {nonce_k, nullptr, nb}, {prehash, nullptr, nb}, {nullptr, sig_rs, 2 * nb},
-                             {nullptr, recovery_id, 1}, {nullptr, ok, 1}};
-    const unsigned fb_flags = (flags & ECGPU_PUBLIC_SCALARS) ? 0u : (flags & ECGPU_EXACT_REFERENCE) ? (unsigned)ECGPU_EXACT_REFERENCE : (unsigned)ECGPU_SECRET_SCALARS;
-    int prc = host_pipeline(c, args, 6, n, ops->pass_units(c, 0, 1, fb_flags), true, [&](void** d, size_t cnt) {
-      return ops->ecdsa_sign(c, (const uint32_t*)d[0], (const uint32_t*)d[1], (const uint32_t*)d[2], (uint32_t*)d[3], (uint8_t*)d[4], (uint8_t*)d[5], cnt,
-                             flags);
-    });
-    return prc;
-  }
-  Buf bd, bk, bz, bs, br, bo;
-  int rc;
-  if (mem == ECGPU_MEM_HOST) { wipe.arm(0, n * nb); wipe.arm(1, n * nb); }
-  if ((rc = buf_in(c, bd, 0, secret_d, n * nb, mem))) return rc;
-  if ((rc = buf_in(c, bk, 1, nonce_k, n * nb, mem))) return rc;
-  if ((rc = buf_in(c, bz, 4, prehash, n * nb, mem))) return rc;
-  if ((rc = buf_out(c, bs, 2, sig_rs, n * 2 * nb, mem))) return rc;
-  if ((rc = buf_out(c, br, 3, recovery_id, n, mem))) return rc;
-  if ((rc = buf_out(c, bo, 5, ok, n, mem))) return rc;
-  if ((rc = ops->ecdsa_sign(c, (const uint32_t*)bd.dev, (const uint32_t*)bk.dev, (const uint32_t*)bz.dev, (uint32_t*)bs.dev, (uint8_t*)br.dev,
-                            (uint8_t*)bo.dev, n, flags)))
-    return rc;
-  if ((rc = buf_finish(c, bs))) return rc;
-  if ((rc = buf_finish(c, br))) return rc;
-  if ((rc = buf_finish(c, bo))) return rc;
-  return finish_host(c, mem);
+  const CallArg args[] = {arg_in(secret_d, nb, ARG_SECRET), arg_in(nonce_k, nb, ARG_SECRET), arg_in(prehash, nb),
+                          arg_out(sig_rs, 2 * nb), arg_out(recovery_id, 1, ARG_OPTIONAL), arg_out(ok, 1)};
+  // the dominant kernel is the nonce's generator multiplication, on the schedule CurveOps::ecdsa_sign picks for these flags
+  const unsigned fb_flags = (flags & ECGPU_PUBLIC_SCALARS) ? 0u : (flags & ECGPU_EXACT_REFERENCE) ? (unsigned)ECGPU_EXACT_REFERENCE : (unsigned)ECGPU_SECRET_SCALARS;
+  return run_batch(c, mem, n, args, ops->pass_units(c, 0, 1, fb_flags), [&](void** d, size_t cnt) {
+    return ops->ecdsa_sign(c, (const uint32_t*)d[0], (const uint32_t*)d[1], (const uint32_t*)d[2], (uint32_t*)d[3], (uint8_t*)d[4], (uint8_t*)d[5], cnt,
+                           flags);
+  });
 }
 
+// the staged secret scalars AND the staged shared values are cleared, whichever way the call ends
 int ecgpu_ecdh_batch(ecgpu_ctx* c, int curve, const uint8_t* secret_d, const uint8_t* pubkeys_xy, uint8_t* shared_x, uint8_t* ok, size_t n, int mem) {
   if (!c || !secret_d || !pubkeys_xy || !shared_x || !ok) return ecgpu_set_err(c, ECGPU_ERR_ARG, "null argument");
   if (n == 0) return ECGPU_OK;
   ENTER(c, curve);
-  SecretWipe wipe(c);                        // the staged secret scalars are cleared on every exit path
-  if (mem == ECGPU_MEM_HOST && n >= PIPE_MIN) {
-    wipe.arm_pipeline(0); wipe.arm_pipeline(2);          // secrets, shared values
-    const PipeArg args[4] = {{secret_d, nullptr, nb}, {pubkeys_xy, nullptr, 2 * nb}, {nullptr, shared_x, nb}, {nullptr, ok, 1}};
-    return host_pipeline(c, args, 4, n, ops->pass_units(c, 1, 1, ECGPU_SECRET_SCALARS), true, [&](void** d, size_t cnt) {
-      return ops->ecdh(c, (const uint32_t*)d[0], (const uint32_t*)d[1], (uint32_t*)d[2], (uint8_t*)d[3], cnt);
-    });
-  }
-  Buf bd, bq, bs, bo;
-  int rc;
-  if (mem == ECGPU_MEM_HOST) { wipe.arm(0, n * nb); wipe.arm(2, n * nb); }   // the staged secrets AND the staged shared values, whichever way the call ends
-  if ((rc = buf_in(c, bd, 0, secret_d, n * nb, mem))) return rc;
-  if ((rc = buf_in(c, bq, 1, pubkeys_xy, n * 2 * nb, mem))) return rc;
-  if ((rc = buf_out(c, bs, 2, shared_x, n * nb, mem))) return rc;
-  if ((rc = buf_out(c, bo, 3, ok, n, mem))) return rc;
-  if ((rc = ops->ecdh(c, (const uint32_t*)bd.dev, (const uint32_t*)bq.dev, (uint32_t*)bs.dev, (uint8_t*)bo.dev, n))) return rc;
-  if ((rc = buf_finish(c, bs))) return rc;
-  if ((rc = buf_finish(c, bo))) return rc;
-  return finish_host(c, mem);
+  const CallArg args[] = {arg_in(secret_d, nb, ARG_SECRET), arg_in(pubkeys_xy, 2 * nb), arg_out(shared_x, nb, ARG_SECRET), arg_out(ok, 1)};
+  return run_batch(c, mem, n, args, ops->pass_units(c, 1, 1, ECGPU_SECRET_SCALARS), [&](void** d, size_t cnt) {
+    return ops->ecdh(c, (const uint32_t*)d[0], (const uint32_t*)d[1], (uint32_t*)d[2], (uint8_t*)d[3], cnt);
+  });
 }
 
 int ecgpu_synth_scalars(ecgpu_ctx* c, int curve, uint64_t seed, uint64_t first, uint8_t* d_scalars, size_t n) {

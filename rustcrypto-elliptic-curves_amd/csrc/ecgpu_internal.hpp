@@ -10,6 +10,23 @@
 
 #include "../../include/ecgpu.h"
 
+// A grow-only device buffer (ecgpu_reserve below): scratch whose contents do not survive growing.
+struct DevBuf {
+  void* p = nullptr;
+  size_t cap = 0;
+};
+// generator tables of a curve, built on first use (curve_ops.hpp)
+enum ecgpu_table_kind {
+  ECGPU_TAB_GEN,      // the reference schedule's table
+  ECGPU_TAB_FB8,      // fixed-base tables of the throughput schedule (fixedbase.hpp): 8-bit windows
+  ECGPU_TAB_FB16,     // 16-bit-window variant for large batches
+  ECGPU_TAB_FB20,     // 20-bit-window variant for very large batches
+  ECGPU_TAB_FB24,     // 24-bit windows (5.9 GB for a 256-bit curve): batches of 2^23 and more
+  ECGPU_TAB_FB26,     // 26-bit windows (21.5 GB): batches of 2^24 and more on the 256-bit curves
+  ECGPU_TAB_FBCT,     // 5-bit windows, read in full by the constant-time kernel (signing)
+  ECGPU_TAB_COUNT_
+};
+
 struct ecgpu_ctx {
   int device = -1;
   int num_cus = 0;
@@ -24,8 +41,7 @@ struct ecgpu_ctx {
   // grow-only device staging buffers for ECGPU_MEM_HOST calls: 6 for whole-batch staging, then PIPE_NSLOT pipeline slots x PIPE_MAXARGS arguments
   static constexpr int PIPE_NSLOT = 3, PIPE_MAXARGS = 6, PIPE_STAGE0 = 6;
   static constexpr int NSTAGE = PIPE_STAGE0 + PIPE_NSLOT * PIPE_MAXARGS;
-  void* stage[NSTAGE] = {};
-  size_t stage_cap[NSTAGE] = {};
+  DevBuf stage[NSTAGE];
   // chunked host-buffer pipeline (host_pipe.hpp): download and upload streams, per-slot events (inputs arrived / kernels done /
   // outputs read), and the page-locked bounce buffers pageable caller memory is copied through ([0] uploads, [1] downloads)
   static constexpr int PIPE_NWORK = 4;
@@ -37,29 +53,18 @@ struct ecgpu_ctx {
   hipEvent_t ev_down[PIPE_NSLOT] = {};
   void* bounce[2][PIPE_NWORK] = {};
   hipEvent_t ev_bounce[2][PIPE_NWORK] = {};
-  // precomputed generator tables, one per curve, built on first use
-  void* gen_table[3] = {nullptr, nullptr, nullptr};
-  // fixed-base tables of the throughput schedule (fixedbase.hpp)
-  void* fb_table[3] = {nullptr, nullptr, nullptr};
-  void* fb16_table[3] = {nullptr, nullptr, nullptr};   // 16-bit-window variant for large batches
-  void* fb20_table[3] = {nullptr, nullptr, nullptr};   // 20-bit-window variant for very large batches
-  void* fbct_table[3] = {nullptr, nullptr, nullptr};   // 5-bit windows, read in full by the constant-time kernel (signing)
-  void* fb24_table[3] = {nullptr, nullptr, nullptr};   // 24-bit windows (5.9 GB for a 256-bit curve): batches of 2^23 and more
-  void* fb26_table[3] = {nullptr, nullptr, nullptr};   // 26-bit windows (21.5 GB): batches of 2^24 and more on the 256-bit curves
+  void* table[ECGPU_TAB_COUNT_][3] = {};             // [kind][curve]
   size_t fb_bytes[3] = {0, 0, 0};                      // device memory held by the generator tables of a curve
   int fb_widest[3] = {0, 0, 0};
   // per-lane table workspace of the k256 variable-base kernel (grow-only)
-  void* tab_ws = nullptr;
-  size_t tab_ws_cap = 0;
+  DevBuf tab_ws;
   // MSM workspace (grow-only)
-  void* msm_ws = nullptr;
-  size_t msm_ws_cap = 0;
+  DevBuf msm_ws;
   // work counters of the dynamically scheduled kernels (sched.hpp): a small ring, one 8-byte counter per launch, zeroed on the stream before it
   unsigned long long* sched_ctr = nullptr;
   unsigned sched_next = 0;
   // intermediate scalars / points of the ECDSA pipelines (grow-only)
-  void* ecdsa_ws = nullptr;
-  size_t ecdsa_ws_cap = 0;
+  DevBuf ecdsa_ws;
 };
 
 static inline int ecgpu_set_err(ecgpu_ctx* c, int code, const char* fmt, ...) {
@@ -77,6 +82,21 @@ static inline int ecgpu_set_err(ecgpu_ctx* c, int code, const char* fmt, ...) {
     hipError_t e_ = (call);                                                                                    \
     if (e_ != hipSuccess) return ecgpu_set_err(c, ECGPU_ERR_RUNTIME, "%s: %s", #call, hipGetErrorString(e_)); \
   } while (0)
+
+// Makes `b` hold at least `need` bytes.  Growing waits for the work queued on the old buffer, frees it and allocates anew: the
+// contents are lost and the new memory is not cleared.
+static inline int ecgpu_reserve(ecgpu_ctx* c, DevBuf& b, size_t need) {
+  if (need <= b.cap) return 0;
+  if (b.p) {
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipFree(b.p));
+  }
+  b.p = nullptr;
+  b.cap = 0;
+  HIPCHK(c, hipMalloc(&b.p, need));
+  b.cap = need;
+  return 0;
+}
 
 // the counter of the next dynamically scheduled launch (sched.hpp), zeroed on the context's stream; nullptr on failure (error text set)
 static inline unsigned long long* ecgpu_sched_counter(ecgpu_ctx* c) {

@@ -145,7 +145,7 @@ static inline int ensure_resources(ecgpu_ctx* c, bool need_bounce_up, bool need_
 struct Piece { int arg; size_t off, len; };     // byte range of one argument's chunk
 
 // stage slot of argument a in pipeline slot s (ecgpu.hip: stage_reserve)
-static inline int stage_index(int slot, int a) { return ecgpu_ctx::PIPE_STAGE0 + slot * ecgpu_ctx::PIPE_MAXARGS + a; }
+static constexpr int stage_index(int slot, int a) { return ecgpu_ctx::PIPE_STAGE0 + slot * ecgpu_ctx::PIPE_MAXARGS + a; }
 
 template <class Reserve, class Launch>
 static int run(ecgpu_ctx* c, const Arg* args, int nargs, const std::vector<size_t>& sizes, bool secret, Reserve reserve, Launch launch) {
@@ -217,7 +217,7 @@ static int run(ecgpu_ctx* c, const Arg* args, int nargs, const std::vector<size_
       const size_t lo = start[ci], cnt = sizes[ci];
       for (int a = 0; a < nargs; a++)
         if (args[a].in && pinned[a]) {
-          hipError_t e = hipMemcpyAsync(c->stage[stage_index(slot, a)], (const char*)args[a].in + lo * args[a].unit, cnt * args[a].unit, hipMemcpyHostToDevice, c->up_stream);
+          hipError_t e = hipMemcpyAsync(c->stage[stage_index(slot, a)].p, (const char*)args[a].in + lo * args[a].unit, cnt * args[a].unit, hipMemcpyHostToDevice, c->up_stream);
           if (e != hipSuccess) return fail(e, "upload");
         }
       if (any_up) {
@@ -227,7 +227,7 @@ static int run(ecgpu_ctx* c, const Arg* args, int nargs, const std::vector<size_
           hipError_t e = hipEventSynchronize(c->ev_bounce[0][w]);          // the previous piece of this buffer has left it
           if (e == hipSuccess) {
             memcpy(c->bounce[0][w], (const char*)args[p.arg].in + lo * args[p.arg].unit + p.off, p.len);
-            e = hipMemcpyAsync((char*)c->stage[stage_index(slot, p.arg)] + p.off, c->bounce[0][w], p.len, hipMemcpyHostToDevice, c->up_stream);
+            e = hipMemcpyAsync((char*)c->stage[stage_index(slot, p.arg)].p + p.off, c->bounce[0][w], p.len, hipMemcpyHostToDevice, c->up_stream);
           }
           if (e == hipSuccess) e = hipEventRecord(c->ev_bounce[0][w], c->up_stream);
           if (e != hipSuccess) fail(e, "upload through the bounce pool");
@@ -258,14 +258,14 @@ static int run(ecgpu_ctx* c, const Arg* args, int nargs, const std::vector<size_
       const size_t lo = start[ci], cnt = sizes[ci];
       for (int a = 0; a < nargs; a++)
         if (args[a].out && pinned[a]) {
-          e = hipMemcpyAsync((char*)args[a].out + lo * args[a].unit, c->stage[stage_index(slot, a)], cnt * args[a].unit, hipMemcpyDeviceToHost, c->copy_stream);
+          e = hipMemcpyAsync((char*)args[a].out + lo * args[a].unit, c->stage[stage_index(slot, a)].p, cnt * args[a].unit, hipMemcpyDeviceToHost, c->copy_stream);
           if (e != hipSuccess) return fail(e, "download");
         }
       if (any_dn) {
         const std::vector<Piece> pieces = pieces_of(ci, false);
         team->parallel_for(pieces.size(), [&](size_t pi, int w) {
           const Piece& p = pieces[pi];
-          hipError_t e2 = hipMemcpyAsync(c->bounce[1][w], (const char*)c->stage[stage_index(slot, p.arg)] + p.off, p.len, hipMemcpyDeviceToHost, c->copy_stream);
+          hipError_t e2 = hipMemcpyAsync(c->bounce[1][w], (const char*)c->stage[stage_index(slot, p.arg)].p + p.off, p.len, hipMemcpyDeviceToHost, c->copy_stream);
           if (e2 == hipSuccess) e2 = hipEventRecord(c->ev_bounce[1][w], c->copy_stream);
           if (e2 == hipSuccess) e2 = hipEventSynchronize(c->ev_bounce[1][w]);
           if (e2 == hipSuccess) memcpy((char*)args[p.arg].out + lo * args[p.arg].unit + p.off, c->bounce[1][w], p.len);
@@ -293,7 +293,7 @@ static int run(ecgpu_ctx* c, const Arg* args, int nargs, const std::vector<size_
     if (e == hipSuccess && ci >= (size_t)NSLOT) e = hipStreamWaitEvent(c->stream, c->ev_down[slot], 0);   // the slot's outputs have been read
     if (e != hipSuccess) { fail(e, "launch: wait"); break; }
     void* dev[ecgpu_ctx::PIPE_MAXARGS];
-    for (int a = 0; a < nargs; a++) dev[a] = (args[a].in || args[a].out) ? c->stage[stage_index(slot, a)] : nullptr;
+    for (int a = 0; a < nargs; a++) dev[a] = (args[a].in || args[a].out) ? c->stage[stage_index(slot, a)].p : nullptr;
     rc = launch(dev, sizes[ci], ci);
     if (rc == 0) {
       e = hipEventRecord(c->ev_kernel[slot], c->stream);

@@ -1033,14 +1033,6 @@ __global__ void __launch_bounds__(256) to_affine_kernel(const u32* xyz, u32* xy,
 #define MSM_ROUNDS 6                 // bucket-sum runs per resident lane (ECGPU_MSM_ROUNDS)
 #endif
 static inline size_t msm_align(size_t x) { return (x + 255) & ~(size_t)255; }
-static int msm_reserve(ecgpu_ctx* c, size_t need) {
-  if (need > c->msm_ws_cap) {
-    if (c->msm_ws) { HIPCHK(c, hipStreamSynchronize(c->stream)); HIPCHK(c, hipFree(c->msm_ws)); c->msm_ws = nullptr; c->msm_ws_cap = 0; }
-    HIPCHK(c, hipMalloc(&c->msm_ws, need));
-    c->msm_ws_cap = need;
-  }
-  return 0;
-}
 
 // the bucket method with CB-bit windows
 template <class C, int CB>
@@ -1085,13 +1077,13 @@ static int msm_buckets(ecgpu_ctx* c, const u32* sc, const u32* pts, int pt_fmt, 
   const size_t sz_ctr = al(16), sz_heavy = al(hmax * sizeof(HeavyBucket)), sz_chunks = al(cmax * sizeof(HeavyChunk)), sz_partial = al(cmax * sizeof(J));
   const size_t need = sz_aff + sz_prep + sz_mag + sz_sgn + sz_off + sz_coff + sz_tot + sz_part + 2 * sz_sorted + sz_bx + 2 * sz_piece + sz_span + 2 * sz_l0 + 2 * sz_l1 + sz_grp +
                       2 * sz_win + sz_ctr + sz_heavy + sz_chunks + sz_partial + sz_big;
-  int rc = msm_reserve(c, need);
+  int rc = ecgpu_reserve(c, c->msm_ws, need);
   if (rc) return rc;
   // the coarse scatter groups its tiles in more LDS than the 64 KB a kernel gets by default (set per call: the attribute
   // belongs to the function on the current device, and a process may hold contexts on several devices)
   HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&coarse_scatter_kernel<CB>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                 (int)sizeof(typename CoarseTile<CB>::Lds)));
-  char* p = (char*)c->msm_ws;
+  char* p = (char*)c->msm_ws.p;
   u32* aff = (u32*)p; p += sz_aff;
   u32* prep = (u32*)p; p += sz_prep;
   Mag* mag = (Mag*)p; p += sz_mag;
@@ -1204,9 +1196,9 @@ static int msm_run(ecgpu_ctx* c, const u32* sc, const u32* pts, int pt_fmt, size
     auto al = msm_align;
     const int blocks = (int)((n + 255) / 256 < 1024 ? (n + 255) / 256 : 1024);
     const size_t sz_prod = al(n * 8 * NW), sz_part = al((size_t)blocks * sizeof(J)), sz_win = al(sizeof(J));
-    int rc = msm_reserve(c, sz_prod + sz_part + sz_win);
+    int rc = ecgpu_reserve(c, c->msm_ws, sz_prod + sz_part + sz_win);
     if (rc) return rc;
-    char* p = (char*)c->msm_ws;
+    char* p = (char*)c->msm_ws.p;
     u32* prod = (u32*)p; p += sz_prod;
     J* partial = (J*)p; p += sz_part;
     J* win = (J*)p;

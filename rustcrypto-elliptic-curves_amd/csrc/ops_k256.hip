@@ -28,12 +28,9 @@ int CurveOps<CurveK256>::lincomb_fast(ecgpu_ctx* c, const u32* sc, const u32* pt
 #else
   const size_t ws_need = (size_t)grid * 256 * sizeof(TabSlotK256) * (terms == 2 ? 2 * K256Win<4>::SLOTS : K256Win<K256_WB>::SLOTS);
 #endif
-  if (ws_need > c->tab_ws_cap) {
-    if (c->tab_ws) { HIPCHK(c, hipStreamSynchronize(c->stream)); HIPCHK(c, hipFree(c->tab_ws)); c->tab_ws = nullptr; c->tab_ws_cap = 0; }
-    HIPCHK(c, hipMalloc(&c->tab_ws, ws_need));
-    c->tab_ws_cap = ws_need;
-  }
-  TabSlotK256* ws = (TabSlotK256*)c->tab_ws;
+  int rc = ecgpu_reserve(c, c->tab_ws, ws_need);
+  if (rc) return rc;
+  TabSlotK256* ws = (TabSlotK256*)c->tab_ws.p;
   unsigned long long* ctr = ecgpu_sched_counter(c);
   if (!ctr) return ECGPU_ERR_RUNTIME;
   if (terms == 2) {

@@ -41,14 +41,6 @@ __global__ void __launch_bounds__(256, WAVES) k256_mul_ct_kernel(const u32* scal
   for (size_t base = tid; base < n; base += T * BATCH) vbct::lane_pass_k256<BATCH>(scalars, points, pt_fmt, out, out_fmt, out_inf, n, base, T, ws, dm);
 }
 
-static int tab_reserve(ecgpu_ctx* c, size_t need) {
-  if (need <= c->tab_ws_cap) return 0;
-  if (c->tab_ws) { HIPCHK(c, hipStreamSynchronize(c->stream)); HIPCHK(c, hipFree(c->tab_ws)); c->tab_ws = nullptr; c->tab_ws_cap = 0; }
-  HIPCHK(c, hipMalloc(&c->tab_ws, need));
-  c->tab_ws_cap = need;
-  return 0;
-}
-
 size_t ecgpuint_k256_ct_pass_units(const ecgpu_ctx* c) { return (size_t)c->num_cus * K256_CT_WAVES * 256 * K256_CT_BATCH; }
 
 int ecgpuint_k256_mul_ct(ecgpu_ctx* c, const uint32_t* sc, const uint32_t* pts, int pt_fmt, uint32_t* out, int out_fmt, uint8_t* out_inf, size_t n) {
@@ -58,10 +50,10 @@ int ecgpuint_k256_mul_ct(ecgpu_ctx* c, const uint32_t* sc, const uint32_t* pts, 
 #define K256_CT_GRID_MULT 4      // ECDH kernel, 2^22 units: 1 / 2 / 4 / 8 = 42.6 / 39.8 / 39.0 / 38.9 ms (profiles/r04_ab_measurements.txt, set seven)
 #endif
   const dim3 grid(ecgpu_grid_for(c, n, K256_CT_WAVES * K256_CT_GRID_MULT));
-  int rc = tab_reserve(c, (size_t)grid.x * 256 * vbct::k256_lane_chunks<K256_CT_BATCH>() * sizeof(vbct::Chunk));
+  int rc = ecgpu_reserve(c, c->tab_ws, (size_t)grid.x * 256 * vbct::k256_lane_chunks<K256_CT_BATCH>() * sizeof(vbct::Chunk));
   if (rc) return rc;
   hipLaunchKernelGGL((k256_mul_ct_kernel<K256_CT_BATCH, K256_CT_WAVES>), grid, dim3(256), 0, c->stream, sc, pts, pt_fmt, out, out_fmt, out_inf, n,
-                     (vbct::Chunk*)c->tab_ws);
+                     (vbct::Chunk*)c->tab_ws.p);
   HIPCHK(c, hipGetLastError());
   return 0;
 }
@@ -93,10 +85,10 @@ int ecgpuint_k256_reference(ecgpu_ctx* c, const uint32_t* sc, const uint32_t* pt
     if (blocks > cap) blocks = cap;
     if (blocks > budget) blocks = budget ? budget : 1;
     const size_t lanes = blocks * 256, sz_tab = (lanes * terms * 16 * sizeof(PtK256) + 255) & ~(size_t)255;
-    int rc = tab_reserve(c, sz_tab + lanes * terms * 10 * sizeof(u32));
+    int rc = ecgpu_reserve(c, c->tab_ws, sz_tab + lanes * terms * 10 * sizeof(u32));
     if (rc) return rc;
     hipLaunchKernelGGL((k256_lincomb_ref_n_kernel<C>), dim3((unsigned)blocks), dim3(256), 0, c->stream, sc, pts, pt_fmt, (int)terms, out, out_fmt, out_inf, n,
-                       (PtK256*)c->tab_ws, (u32*)((char*)c->tab_ws + sz_tab));
+                       (PtK256*)c->tab_ws.p, (u32*)((char*)c->tab_ws.p + sz_tab));
   }
   HIPCHK(c, hipGetLastError());
   return 0;

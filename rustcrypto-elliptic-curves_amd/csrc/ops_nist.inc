@@ -38,17 +38,17 @@ int CurveOps<ECGPU_NIST_CURVE>::lincomb_fast(ecgpu_ctx* c, const u32* sc, const 
     // per-lane workspace (VBB tables of 8 points and the prefix products of their shared inversion per resident lane),
     // grow-only, shared with the other curves' kernels
     constexpr int WB = VB_WINDOW(C);
-    int rc = tab_reserve(c, (size_t)grid.x * 256 * (terms == 2 ? sizeof(vb::LaneWs<C, VBB>) : sizeof(vb::LaneWs<C, VBB, WB>)));
+    int rc = ecgpu_reserve(c, c->tab_ws, (size_t)grid.x * 256 * (terms == 2 ? sizeof(vb::LaneWs<C, VBB>) : sizeof(vb::LaneWs<C, VBB, WB>)));
     if (rc) return rc;
     unsigned long long* ctr = ecgpu_sched_counter(c);
     if (!ctr) return ECGPU_ERR_RUNTIME;
     const WaveSched sched{ctr, (unsigned long long)n, grid.x * 4u, (unsigned)(terms == 2 ? VB_CHUNK_UNITS / 2 : VB_CHUNK_UNITS), 1u};
     if (terms == 2)
-      hipLaunchKernelGGL((vb::mul_kernel<C, VBB, VB_WAVES, 2>), grid, dim3(256), 0, c->stream, sc, pts, pt_fmt, out, out_fmt, out_inf, n, (vb::LaneWs<C, VBB>*)c->tab_ws,
+      hipLaunchKernelGGL((vb::mul_kernel<C, VBB, VB_WAVES, 2>), grid, dim3(256), 0, c->stream, sc, pts, pt_fmt, out, out_fmt, out_inf, n, (vb::LaneWs<C, VBB>*)c->tab_ws.p,
                          sched);
     else
       hipLaunchKernelGGL((vb::mul_kernel<C, VBB, VB_WAVES, 1, WB>), grid, dim3(256), 0, c->stream, sc, pts, pt_fmt, out, out_fmt, out_inf, n,
-                         (vb::LaneWs<C, VBB, WB>*)c->tab_ws, sched);
+                         (vb::LaneWs<C, VBB, WB>*)c->tab_ws.p, sched);
     HIPCHK(c, hipGetLastError());
     return 1;
   }
@@ -66,12 +66,9 @@ int CurveOps<ECGPU_NIST_CURVE>::mul_ct(ecgpu_ctx* c, const u32* sc, const u32* p
 #endif
   const dim3 grid(ecgpu_grid_for(c, n, WAVES * VBCT_GRID_MULT));
   const size_t ws_need = (size_t)grid.x * 256 * vbct::lane_chunks<C, VBB>() * sizeof(vbct::Chunk);
-  if (ws_need > c->tab_ws_cap) {
-    if (c->tab_ws) { HIPCHK(c, hipStreamSynchronize(c->stream)); HIPCHK(c, hipFree(c->tab_ws)); c->tab_ws = nullptr; c->tab_ws_cap = 0; }
-    HIPCHK(c, hipMalloc(&c->tab_ws, ws_need));
-    c->tab_ws_cap = ws_need;
-  }
-  hipLaunchKernelGGL((vbct::mul_kernel<C, VBB, WAVES>), grid, dim3(256), 0, c->stream, sc, pts, pt_fmt, out, out_fmt, out_inf, n, (vbct::Chunk*)c->tab_ws);
+  int rc = ecgpu_reserve(c, c->tab_ws, ws_need);
+  if (rc) return rc;
+  hipLaunchKernelGGL((vbct::mul_kernel<C, VBB, WAVES>), grid, dim3(256), 0, c->stream, sc, pts, pt_fmt, out, out_fmt, out_inf, n, (vbct::Chunk*)c->tab_ws.p);
   HIPCHK(c, hipGetLastError());
   return 1;
 }
