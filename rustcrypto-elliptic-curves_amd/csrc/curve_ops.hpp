@@ -14,17 +14,14 @@
 // the inversion's share is large: measured at 2^24 scalars, batch 16 / 32 / 64: p256 0.96 / 1.03 / 1.06, k256 1.19 /
 // 1.24 / 1.25 x 10^9 per second; p384 (2^22) 282 / 280 / 279 x 10^6 (its results are 144 bytes each in the private
 // segment), hence 16 there.
-#ifndef ECGPU_REF_GRID_MULT
-#define ECGPU_REF_GRID_MULT 4
-#endif
 #ifndef FB_BATCH
 #define FB_BATCH (C::NW > 8 ? 16 : 64)
 #endif
-// occupancy target of the wide fixed-base kernel (A/B switch: 3 = 168 VGPRs, room for the gather prefetch ECGPU_FB_PREFETCH)
 // results per lane a wave of the wide fixed-base kernel draws at a time (sched.hpp): 16 results are about one variable-base unit's work
 #ifndef FB_CHUNK_UNITS
 #define FB_CHUNK_UNITS 16
 #endif
+// occupancy target of the wide fixed-base kernel (3 = 168 VGPRs: 13.0-13.3 ms per 2^24 on P-256 against 12.5-12.6 at 4, fixedbase.hpp)
 #ifndef FB_WIDE_WAVES
 #define FB_WIDE_WAVES 4
 #endif
@@ -34,10 +31,6 @@
 // round-2 targets 3 / 4 / 2: k256 4.66 vs 4.72 ms, p384 16.4 vs 17.1 ms (profiles/r03_ab_measurements.txt)
 #ifndef FBCT_WAVES
 #define FBCT_WAVES(C) (C::NW > 8 ? 3 : 4)
-#endif
-// most workgroups launched per resident one by the constant-time fixed-base kernel (ecgpu_grid_oversubscribed; profiles/r04_ab_measurements.txt, set nine)
-#ifndef FBCT_GRID_MULT
-#define FBCT_GRID_MULT 4
 #endif
 
 namespace ecgpu {
@@ -168,6 +161,8 @@ struct CurveOps {
     if (rc) return rc;
     unsigned long long* ctr = ecgpu_sched_counter(c);
     if (!ctr) return ECGPU_ERR_RUNTIME;
+    // a chunk of 0 results never advances the work counter (the kernel hangs); one above the batch overruns the result buffer before its flush test
+    static_assert(FB_CHUNK_UNITS >= 1 && FB_CHUNK_UNITS <= (FB_BATCH), "FB_CHUNK_UNITS must lie in 1 .. FB_BATCH");
     const unsigned grid = ecgpu_grid_for(c, n, FB_WIDE_WAVES);
     hipLaunchKernelGGL((fb::mul_wide_kernel<C, WB, FB_BATCH, FB_WIDE_WAVES>), dim3(grid), dim3(256), 0, c->stream, sc,
                        (const AffEntry<C>*)*slot, out, out_fmt, out_inf, n, WaveSched{ctr, (unsigned long long)n, grid * 4u, (unsigned)FB_CHUNK_UNITS, 1u});

@@ -308,12 +308,8 @@ __global__ void __launch_bounds__(256, WAVES) mul_wide_kernel(const u32* scalars
       // Software pipeline over the gathers (round 4): the entry of window j + 1 is in flight during the addition of window j.  16 more
       // live registers (128 VGPRs, 7 spilled on P-256); p256 fixed base 2^24: 12.48-12.59 ms against 12.65-12.76 (-1.6 %, three alternating
       // passes, profiles/r04_ab_measurements.txt); at 3 waves per SIMD with or without it: 13.0-13.3 ms.  P-384's 24 extra registers cost
-      // it 18 % (round 2): the plain loop stays there.  ECGPU_FB_NO_PREFETCH: A/B switch.
-#ifdef ECGPU_FB_NO_PREFETCH
-      constexpr bool PREFETCH = false;
-#else
+      // it 18 % (round 2): the plain loop stays there.
       constexpr bool PREFETCH = (NW <= 8);
-#endif
       if constexpr (PREFETCH) {
         int nsd = digit(0);
         typename C::Fe nx, ny;
@@ -380,6 +376,11 @@ __global__ void __launch_bounds__(256, WAVES) mul_wide_kernel(const u32* scalars
 //   * one inversion per BATCH results (Montgomery's trick on the homogeneous Z; a zero Z is masked to 1 and flagged).
 // 52 (77) additions of 8M + 3S instead of the reference schedule's 256 (384) doublings and 64 (96) additions.
 // ---------------------------------------------------------------------------------------------------------------------
+// most workgroups launched per resident one by this kernel's launchers (curve_ops.hpp, ops_k256_ct.hip: ecgpu_grid_oversubscribed;
+// profiles/r04_ab_measurements.txt, set nine)
+#ifndef FBCT_GRID_MULT
+#define FBCT_GRID_MULT 4
+#endif
 template <class C, int BATCH, int WAVES>
 __global__ void __launch_bounds__(256, WAVES) mul_ct_kernel(const u32* scalars, const AffEntry<C>* table, u32* out, int out_fmt, uint8_t* out_inf, size_t n) {
   constexpr int NW = C::NW;

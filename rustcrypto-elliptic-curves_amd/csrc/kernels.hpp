@@ -182,6 +182,9 @@ __global__ void __launch_bounds__(256) normalize_kernel(const u32* p, u32* out_x
 #ifndef ECGPU_REF_WAVES
 #define ECGPU_REF_WAVES 2          // occupancy target of the reference-schedule kernels (measured: see DESIGN.md section 4)
 #endif
+#ifndef ECGPU_REF_GRID_MULT
+#define ECGPU_REF_GRID_MULT 4      // workgroups their launchers (curve_ops.hpp, ops_k256_ct.hip) start per resident one: the kernels walk their units one at a time
+#endif
 template <class C, int NT>
 __global__ void __launch_bounds__(256, ECGPU_REF_WAVES) lincomb_ref_kernel(const u32* scalars, const u32* points, int pt_fmt,
                                                           u32* out, int out_fmt, uint8_t* out_inf, size_t n) {
@@ -337,12 +340,6 @@ __device__ __forceinline__ void k256_fast_loop(JacK256* out, const K256FastPrep*
   *out = acc;
 }
 
-// Montgomery's trick over the cnt results of this lane; element j of the batch is global index base + j*T.
-__device__ __forceinline__ void k256_fast_finish(const JacK256* res, FeK256* pre, int cnt, size_t base, size_t T, u32* out, int out_fmt,
-                                              uint8_t* out_inf) {
-  jac::store_batch_affine<CurveK256>(res, pre, cnt, base, T, out, out_fmt, out_inf);
-}
-
 // Two-term linear combination k0*P0 + k1*P1 sharing the 128 doublings (LinearCombination::lincomb,
 // k256 mul.rs:313-323 with N = 2: the ECDSA-verify shape u1*G + u2*Q).  Each term gets its own common-Z
 // table; the two tables live on curves isomorphic by different factors, so each is rescaled by the other's
@@ -426,34 +423,10 @@ __global__ void __launch_bounds__(256, WAVES) k256_mul_fast_kernel(const u32* sc
   // this lane's table: 32 slots x 64 B, contiguous, in the launch's global workspace (gridDim * 256 lanes)
   constexpr int WB = K256_WB;
   TabSlotK256* tab = table_ws + ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * K256Win<WB>::SLOTS;
-#ifdef K256_BLOCK_TIMES              // DIAGNOSTIC build: every workgroup records when it started and ended and where it ran, behind the table workspace
-  unsigned long long* blk_times = (unsigned long long*)(table_ws + (size_t)gridDim.x * blockDim.x * K256Win<WB>::SLOTS) + 4 * (size_t)blockIdx.x;
-  if (threadIdx.x == 0) {
-    blk_times[0] = wall_clock64();
-    blk_times[2] = __builtin_amdgcn_s_getreg((31 << 11) | 4);        // HW_ID: wave, simd, pipe, cu, sh, se
-    blk_times[3] = __builtin_amdgcn_s_getreg((31 << 11) | 20);       // XCC_ID
-  }
-#endif
   K256FastPrep prep;
   JacK256 res[BATCH];
   FeK256 pre[BATCH];
   const int pw = (pt_fmt == FMT_PROJECTIVE ? 3 : 2) * 8;
-#ifdef ECGPU_STATIC_GRID_STRIDE      // A/B switch: the static assignment of rounds 1-3 (every lane the same number of units, grid stride)
-  const size_t T = (size_t)gridDim.x * blockDim.x;
-  const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  for (size_t base = tid; base < n; base += T * BATCH) {
-    int cnt = 0;
-#pragma unroll 1
-    for (int j = 0; j < BATCH; j++) {
-      const size_t i = base + (size_t)j * T;
-      if (i >= n) break;
-      k256_fast_prep<WB>(&prep, tab, scalars + i * 8, points + i * pw, pt_fmt);
-      k256_fast_loop<WB>(&res[j], &prep, tab);
-      cnt = j + 1;
-    }
-    k256_fast_finish(res, pre, cnt, base, T, out, out_fmt, out_inf);
-  }
-#else
   // Every wave draws small chunks of 64 x u consecutive units (sched.hpp): lane l takes units lo + l, lo + l + 64, ..; the results stay in res[]
   // across chunks and are flushed - ONE shared inversion - when the buffer is full or the work has run out.
   size_t idx[BATCH];                 // global index of every buffered result
@@ -479,11 +452,6 @@ __global__ void __launch_bounds__(256, WAVES) k256_mul_fast_kernel(const u32* sc
     }
     if (!more) break;
   }
-#endif
-#ifdef K256_BLOCK_TIMES
-  __syncthreads();
-  if (threadIdx.x == 0) blk_times[1] = wall_clock64();
-#endif
 }
 
 template <class C>

@@ -169,14 +169,10 @@ ECGPU_HD void acc_sub32(Acc96& c, u32 w) {
 // just popped or zeroed); the first carry then produces c.hi instead of adding to it, which saves zeroing a register
 // per column.  NC: the caller knows that the first NC products cannot carry out of c.lo (each call site states the bound);
 // they are issued without their carry addition.
-#ifndef ECGPU_MAC_FRESH
-#define ECGPU_MAC_FRESH 1          // 0: always read c.hi (A/B switch for tools/nopbench)
-#endif
-template <int M, bool FRESH_ARG = false, int NC = 0>
+template <int M, bool FRESH = false, int NC = 0>
 ECGPU_HD void mac_cols(Acc96& c, const u32* pa, const u32* pb) {
   static_assert(M >= 1, "column length");
   static_assert(NC >= 0 && NC <= 2 && NC <= M, "at most two leading products without a carry");
-  constexpr bool FRESH = FRESH_ARG && (ECGPU_MAC_FRESH != 0);
   if constexpr (M > 12) {            // an asm statement takes at most 30 operands: split long columns
     mac_cols<12, FRESH, NC>(c, pa, pb);
     mac_cols<M - 12, false>(c, pa + 12, pb + 12);

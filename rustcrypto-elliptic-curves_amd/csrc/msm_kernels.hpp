@@ -565,10 +565,9 @@ struct HeavyBucket { u32 bucket, base, chunks; };
 struct HeavyChunk { u32 bucket, index; };
 
 // the prepared point an entry names: 2 NW words in the field's internal form (16-byte loads)
-// A/B switches of the bucket sums (tools/ab_round3b.sh; DESIGN.md section 4 "MSM: round 3"):
-//   MSM_BS_WAVES     occupancy target (waves per SIMD).  3 = 150 VGPRs and no spill instead of 128 + 110 spilled: 2.5 % SLOWER.
-//   MSM_HOT_GATHER   DIAGNOSTIC ONLY (wrong sums): the term index of every gather is masked with this value, so the gathers
-//                    come from a footprint of (mask + 1) x 64 bytes per half - what the gathers cost, by the cache level they hit.
+// MSM_BS_WAVES: occupancy target of the bucket sums (waves per SIMD).  3 = 150 VGPRs and no spill instead of 128 + 110 spilled: 2.5 % SLOWER
+// (DESIGN.md section 4 "MSM: round 3").  What the gathers cost by the cache level they hit was measured with the diagnostic patches
+// tools/experiments/msm_hot_gather.patch and msm_one_array.patch.
 #ifndef MSM_BS_WAVES
 #define MSM_BS_WAVES 4
 #endif
@@ -576,15 +575,7 @@ template <class C>
 struct RawPoint { uint4 v[C::NW / 2]; };
 template <class C, int CB>
 __device__ __forceinline__ RawPoint<C> entry_point(const u32* prep, size_t n, u32 e) {
-#ifdef MSM_HOT_GATHER
-  const uint4* src = (const uint4*)(prep + ((size_t)((e >> 30) & 1u) * n + (e & (u32)MSM_HOT_GATHER)) * 2 * C::NW);
-#elif defined(MSM_DIAG_ONE_ARRAY)
-  // DIAGNOSTIC ONLY (wrong sums, round 4): both GLV halves gather from half 0's array - what halving the gathers' footprint
-  // (1 GB -> 512 MB at 2^23 terms) would buy at most, before the sort is made half-aware to do it for real
-  const uint4* src = (const uint4*)(prep + (size_t)(e & Geo<CB>::INDEX_MASK) * 2 * C::NW);
-#else
   const uint4* src = (const uint4*)(prep + ((size_t)((e >> 30) & 1u) * n + (e & Geo<CB>::INDEX_MASK)) * 2 * C::NW);
-#endif
   RawPoint<C> r;
 #pragma unroll
   for (int q = 0; q < C::NW / 2; q++) r.v[q] = src[q];

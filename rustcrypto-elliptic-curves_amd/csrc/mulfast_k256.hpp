@@ -31,6 +31,7 @@ struct alignas(16) TabSlotK256 {
 };
 // ECGPU_K256_NO_BETA_SLOTS (A/B switch): 8 slots of (x, y) only, 512 B per lane; the lambda half multiplies x by beta when it
 // reads an entry (one more multiplication on half of the additions) instead of keeping beta*x beside x (1 KB per lane).
+// Stays a switch where the settled experiments were retired ("Retired switches"): equal time for half the table bytes.
 // Window width of the throughput schedule in bits (template parameter WB of the table / digit functions below).  4 (rounds 1-3): table
 // [P .. 8P], 33 digit positions per GLV half (32 signed nibbles and the carry digit), 4 doublings per position.  5 (round 4): table [P .. 16P],
 // 26 positions (5-bit fields of |k_i| + 0x...1084210842 minus 16; |k_i| < 2^128 leaves the top field room for the last carry), 5 doublings per
@@ -56,8 +57,8 @@ constexpr int K256_DW = 5;                                        // recoded wor
 
 namespace k256 {
 
-// In-place doubling, a = 0 (3M + 4S; with the fused Y3 below 4M + 3S of which two multiplications share one reduction), ordered for a
-// short live set (at most five field elements): A = X^2, B = Y^2, Z3 = 2 Y Z, D = 4 X B, C = B^2, E = 3 A, X3 = E^2 - 2D, Y3 = E (D - X3) - 8C.
+// In-place doubling, a = 0 (4M + 3S of which two multiplications share one reduction: the 3M + 4S formula with C = B^2 folded into Y3), ordered
+// for a short live set (at most five field elements): A = X^2, B = Y^2, Z3 = 2 Y Z, D = 4 X B, E = 3 A, X3 = E^2 - 2D, Y3 = E (D - X3) - 8 B^2.
 // Infinity (Z = 0) stays infinity; secp256k1 has no point with Y = 0.
 ECGPU_HD void jac_double(JacK256& p) {
   FeK256 a, b, t;
@@ -65,23 +66,14 @@ ECGPU_HD void jac_double(JacK256& p) {
   sqr(b, p.y);
   mul(p.z, p.y, p.z); shl<1>(p.z, p.z);      // Z3
   mul(p.y, p.x, b); shl<2>(p.y, p.y);        // D (in p.y)
-#ifndef ECGPU_K256_NO_FUSED_DBL                  // Y3 = E (D - X3) + B (-8B) as one fused sum of two products: the squaring C = B^2 rides on the columns of the
-                                                 // multiplication and shares its reduction (+0.5 % on the headline, +1.2 % on the constant-time kernel; A/B switch, tools/ab_round3h.sh)
+  // Y3 = E (D - X3) + B (-8B) as one fused sum of two products: the squaring C = B^2 rides on the columns of the multiplication and
+  // shares its reduction (+0.5 % on the headline, +1.2 % on the constant-time kernel against a separate squaring and subtraction)
   shl<1>(t, a); add(a, t, a);                // E (in a)
   sqr(t, a);
   sub(t, t, p.y); sub(p.x, t, p.y);          // X3 = E^2 - 2D
   sub(p.y, p.y, p.x);                        // D - X3
   shl<3>(t, b); neg(t, t);                   // -8B
   mul_add2(p.y, a, p.y, b, t);               // E (D - X3) - 8 B^2
-#else
-  sqr(b, b);                                 // C
-  shl<1>(t, a); add(a, t, a);                // E (in a)
-  sqr(t, a);
-  sub(t, t, p.y); sub(p.x, t, p.y);          // X3 = E^2 - 2D
-  sub(p.y, p.y, p.x); mul(p.y, a, p.y);      // E (D - X3)
-  shl<3>(b, b);                              // 8C
-  sub(p.y, p.y, b);
-#endif
 }
 ECGPU_HD void jac_double(JacK256& r, const JacK256& p) { r = p; jac_double(r); }
 
@@ -147,15 +139,9 @@ ECGPU_HD void jac_add_mixed(JacK256& p, const FeK256& x2, const FeK256& y2, FeK2
   mul(t, p.x, t);                            // V
   sqr(u, r);
   sub(u, u, h); sub(u, u, t); sub(p.x, u, t);    // X3 = R^2 - HHH - 2V
-#ifdef ECGPU_K256_NO_FUSED_Y3                    // A/B switch (tools/ab_round3f.sh): two multiplications, two reductions and a subtraction
-  sub(t, t, p.x); mul(t, r, t);              // R (V - X3)
-  mul(h, p.y, h);                            // Y1 HHH
-  sub(p.y, t, h);
-#else
   sub(t, t, p.x);                            // V - X3
   neg(u, p.y);
-  mul_add2(p.y, r, t, u, h);                 // Y3 = R (V - X3) + (-Y1) HHH: both products on one set of columns, ONE reduction
-#endif
+  mul_add2(p.y, r, t, u, h);                 // Y3 = R (V - X3) + (-Y1) HHH: both products on one set of columns, ONE reduction (+0.95 % against two)
 }
 ECGPU_HD void jac_add_mixed(JacK256& r, const JacK256& p, const FeK256& x2, const FeK256& y2, FeK256* zr) {
   r = p;

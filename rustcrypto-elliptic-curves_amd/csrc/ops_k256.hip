@@ -8,6 +8,8 @@ using namespace ecgpu;
 #ifndef K256_FAST_BATCH
 #define K256_FAST_BATCH 32   // results per lane that share one inversion in the variable-base kernel (16: -0.4 %)
 #endif
+// a chunk of 0 units never advances the work counter (the kernel hangs); a chunk above the batch overruns the result buffer before its flush test
+static_assert(K256_CHUNK_UNITS >= 1 && K256_CHUNK_UNITS <= K256_FAST_BATCH, "K256_CHUNK_UNITS must lie in 1 .. K256_FAST_BATCH");
 
 template <>
 int CurveOps<CurveK256>::lincomb_fast(ecgpu_ctx* c, const u32* sc, const u32* pts, int pt_fmt, size_t terms, u32* out, int out_fmt,
@@ -17,17 +19,9 @@ int CurveOps<CurveK256>::lincomb_fast(ecgpu_ctx* c, const u32* sc, const u32* pt
   if (!pts) return 0;
   // ECGPU_OPT_K256_WAVES (3 / 4) picks the occupancy variant; default chosen from measurements (profiles/r01_kbench_variants.txt)
   const int waves = c->opt[ECGPU_OPT_K256_WAVES] == 3 ? 3 : 4;
-#ifdef K256_GRID_PER_CU            // A/B switch: workgroups per CU of the single-term kernel's launch, whatever its occupancy target
-  const unsigned grid = ecgpu_grid_for(c, n, terms == 2 ? 4 : K256_GRID_PER_CU);
-#else
   const unsigned grid = ecgpu_grid_for(c, n, terms == 2 ? 4 : waves);
-#endif
   // per-lane table workspace: 2 KB per resident lane for the single-term kernel (16 entries and their beta slots: 537 MB at 4 waves/SIMD), 2 x 1 KB for the two-term kernel
-#ifdef K256_BLOCK_TIMES
-  const size_t ws_need = (size_t)grid * 256 * sizeof(TabSlotK256) * (terms == 2 ? 2 * K256Win<4>::SLOTS : K256Win<K256_WB>::SLOTS) + (size_t)grid * 32 + 16;
-#else
   const size_t ws_need = (size_t)grid * 256 * sizeof(TabSlotK256) * (terms == 2 ? 2 * K256Win<4>::SLOTS : K256Win<K256_WB>::SLOTS);
-#endif
   int rc = ecgpu_reserve(c, c->tab_ws, ws_need);
   if (rc) return rc;
   TabSlotK256* ws = (TabSlotK256*)c->tab_ws.p;

@@ -5,7 +5,9 @@
 // a value derived from a secret (missing 4).  What branches remain are loop counters and the public batch size
 // (profiles/r04_k256_ct_branches.txt lists every s_cbranch of these kernels with the comparison that feeds it).
 // The throughput kernels (ops_k256.hip) keep the branches: they are measurably cheaper and their data is public.
-#ifndef ECGPU_K256_CT_KEEP_BRANCHES        // A/B switch (make ab-ctbranch): the same kernels with the rare carry paths as branches, for the cost and the counters
+// ECGPU_K256_CT_KEEP_BRANCHES (make ab-ctbranch): the same kernels with the rare carry paths as branches, for the cost and the counters.  Not a retired
+// experiment ("Retired switches"): the constant-time evidence is the comparison of the two builds.
+#ifndef ECGPU_K256_CT_KEEP_BRANCHES
 #define ECGPU_K256_BRANCHFREE 1
 #endif
 #include "ecgpu_internal.hpp"
@@ -14,9 +16,6 @@
 #include "varbase_ct_k256.hpp"
 using namespace ecgpu;
 
-#ifndef ECGPU_REF_GRID_MULT
-#define ECGPU_REF_GRID_MULT 4
-#endif
 #ifndef K256_CT_BATCH
 #define K256_CT_BATCH 16
 #endif
@@ -25,9 +24,6 @@ using namespace ecgpu;
 #endif
 #ifndef K256_FBCT_WAVES
 #define K256_FBCT_WAVES 4      // curve_ops.hpp FBCT_WAVES for 8-word fields
-#endif
-#ifndef FBCT_GRID_MULT
-#define FBCT_GRID_MULT 4        // as in curve_ops.hpp
 #endif
 
 template <int BATCH, int WAVES>

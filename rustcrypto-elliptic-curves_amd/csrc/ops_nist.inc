@@ -17,6 +17,10 @@
 #ifndef VB_CHUNK_UNITS
 #define VB_CHUNK_UNITS 2      // P-384, 2^22 units: 1 / 2 / 3 / 4 / 8 / 16 units per draw = 229.6 / 225.5 / 226.1 / 228.1 / 237.4 / 243.0 ms (16 = the static assignment); P-256 73.9-74.2 against 74.0-74.4 at 4
 #endif
+// a chunk of 0 units never advances the work counter (the kernel hangs: the two-term launch draws VB_CHUNK_UNITS / 2, which is 0 for 1); a chunk above
+// the VBB / terms units a lane buffers overruns its result buffer before the flush test
+static_assert(VB_CHUNK_UNITS >= 1 && VB_CHUNK_UNITS <= VBB, "one term: VB_CHUNK_UNITS must lie in 1 .. VBB");
+static_assert(VB_CHUNK_UNITS / 2 >= 1 && VB_CHUNK_UNITS / 2 <= VBB / 2, "two terms: VB_CHUNK_UNITS / 2 must lie in 1 .. VBB / 2 (VB_CHUNK_UNITS = 1 hangs the kernel)");
 #ifndef VB_WAVES
 #define VB_WAVES 4     // occupancy target of the public-data variable-base kernels (waves per SIMD): 3 measured equal (P-384) or 2 % worse (P-256)
 #endif

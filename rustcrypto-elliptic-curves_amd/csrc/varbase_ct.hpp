@@ -252,14 +252,8 @@ ECGPU_HD void lane_pass(const u32* scalars, const u32* points, int pt_fmt, u32* 
     u32 k[NW];
     const u32 flip = scalar_fold<C>(k, scalars + i * NW);
     u32 c = 0;
-#ifdef ECGPU_DIGITS_IN_REGISTERS                 // A/B switch: NW VGPRs and a select chain per read
-    u32 y[NW];
-#pragma unroll
-    for (int w = 0; w < NW; w++) y[w] = addc(k[w], 0x88888888u, c);
-#else
 #pragma unroll
     for (int w = 0; w < NW; w++) dm.st(w, addc(k[w], 0x88888888u, c));       // the recoded digits leave the registers (DigitMem)
-#endif
     Jac<C> acc;
     jac::set_infinity<C>(acc);
     u32 acc_inf = 0xFFFFFFFFu;                 // mask: the accumulator is still empty
@@ -269,13 +263,7 @@ ECGPU_HD void lane_pass(const u32* scalars, const u32* points, int pt_fmt, u32* 
 #pragma unroll 1
         for (int d = 0; d < 4; d++) jac::dbl<C>(acc);
       }
-#ifdef ECGPU_DIGITS_IN_REGISTERS
-      u32 word = 0;
-#pragma unroll
-      for (int q = 0; q < NW; q++) word = ((j >> 3) == q) ? y[q] : word;
-#else
       const u32 word = dm.ld(j == 8 * NW ? 0 : (j >> 3));                       // the address is public (the loop counter)
-#endif
       const u32 nib = (word >> (4 * (j & 7))) & 15u;
       const int sd = (j == 8 * NW) ? (int)c : (int)nib - 8;
       const u32 sgn = (u32)(sd >> 31), mag = ((u32)sd ^ sgn) - sgn;               // |digit| in 0..8
@@ -310,10 +298,8 @@ ECGPU_HD void lane_pass(const u32* scalars, const u32* points, int pt_fmt, u32* 
     fe_mask_select<C>(acc.z, inf, one, acc.z);          // keep the shared inversion clean
     jac_st<C>(ws, entry_chunk<C>(b, 0), acc);
   }
-#ifndef ECGPU_DIGITS_IN_REGISTERS
 #pragma unroll
   for (int w = 0; w < NW; w++) dm.st(w, 0u);            // the last unit's recoded scalar does not stay in LDS
-#endif
   // ---- phase D: x = X / Z^2, y = Y / Z^3 with one inversion for the cnt results of this lane
   {
     Fe run = one;

@@ -165,9 +165,6 @@ ECGPU_HD void lane_pass(const u32* scalars, const u32* points, int pt_fmt, u32* 
     // signed nibbles: digit_j = nibble_j(k + 0x88..8) - 8, the carry out of the top nibble is the last digit
     // (the recoded words go to DigitMem - LDS on the device - instead of NT * NW registers held across the whole loop)
     u32 carry[NT];
-#ifdef ECGPU_DIGITS_IN_REGISTERS                 // A/B switch: the round-2 form (NT * NW VGPRs and a select chain per read)
-    u32 y[NT][NW];
-#endif
 #pragma unroll
     for (int tt = 0; tt < NT; tt++) {
       const int s = b * NT + tt;
@@ -182,11 +179,7 @@ ECGPU_HD void lane_pass(const u32* scalars, const u32* points, int pt_fmt, u32* 
 #pragma unroll
         for (int w = 0; w < NW; w++) {
           const u32 yw = addc(k[w], 0x88888888u, c);
-#ifdef ECGPU_DIGITS_IN_REGISTERS
-          y[tt][w] = skip ? 0x88888888u : yw;
-#else
           dm.st(tt * NW + w, skip ? 0x88888888u : yw);
-#endif
         }
         carry[tt] = skip ? 0u : c;
       } else {
@@ -220,15 +213,7 @@ ECGPU_HD void lane_pass(const u32* scalars, const u32* points, int pt_fmt, u32* 
 #pragma unroll
             for (int q = 0; q < NT; q++) sd = (q == tt) ? (int)carry[q] : sd;
           } else {
-#ifdef ECGPU_DIGITS_IN_REGISTERS
-            u32 word = y[0][0];
-#pragma unroll
-            for (int r = 0; r < NT; r++)
-#pragma unroll
-              for (int q = 0; q < NW; q++) word = (r == tt && (j >> 3) == q) ? y[r][q] : word;
-#else
             const u32 word = dm.ld(tt * NW + (j >> 3));
-#endif
             sd = (int)((word >> (4 * (j & 7))) & 15u) - 8;
           }
         } else {

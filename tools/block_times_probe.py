@@ -1,5 +1,8 @@
-"""DIAGNOSTIC (libecgpu_bt<k>.so: -DK256_BLOCK_TIMES): when did every workgroup of the headline kernel start and end, and on which XCD / SE / CU?
-Usage: ECGPU_LIB=.../lib_exp/libecgpu_bt4.so python tools/block_times_probe.py <workgroups per CU>"""
+"""DIAGNOSTIC: when did every workgroup of the headline kernel start and end, and on which XCD / SE / CU?
+Only meaningful with tools/experiments/k256_block_times.patch applied (git apply, then make variant NAME=bt4 TU=ops_k256 with the define the
+patch's header names): the patched kernel writes four words per workgroup behind the table workspace, which this script reads back.  On the
+product library the same bytes are table entries and the printed times are garbage.  Results: profiles/r04_ab_measurements.txt, set six.
+Usage: ECGPU_LIB=.../lib_exp/libecgpu_bt4.so python tools/block_times_probe.py <workgroups per CU>   (4 unless the variant sets the patch's grid define)"""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "rustcrypto-elliptic-curves_amd"))
