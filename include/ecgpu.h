@@ -190,7 +190,7 @@ int ecgpu_host_free(ecgpu_ctx* ctx, void* p);
 int ecgpu_host_chunk_schedule(size_t n, size_t pass_units, size_t* sizes, size_t cap);
 
 /* Diagnostic: size and contents of a context's grow-only device workspaces (which = 0: per-lane table workspace of the
- * variable-base kernels, 1: intermediate scalars / points of the ECDSA / ECDH pipelines, 2: MSM workspace, 16 + i: staging slot i of
+ * variable-base kernels, 1: intermediate scalars / points of the ECDSA / ECDH / hash pipelines, 2: MSM workspace, 3: BIP340 challenges, 16 + i: staging slot i of
  * host-buffer calls; 16 + 6 + 6 s + a is argument a of pipeline slot s).  *bytes = the workspace's size (0 if it does not exist
  * yet); if host_copy is not NULL the first min(cap, size) bytes are copied into it after the context's stream has drained.
  * For audits of secret hygiene: the tests read the workspaces back after secret-scalar calls and check that no result, prefix
@@ -379,12 +379,54 @@ int ecgpu_ecdh_batch(ecgpu_ctx* ctx, int curve, const uint8_t* secret_scalars, c
 int ecgpu_schnorr_verify_batch(ecgpu_ctx* ctx, int curve, const uint8_t* pubkeys_x, const uint8_t* sig_rs,
                                const uint8_t* challenges, uint8_t* ok, size_t n, int mem);
 
-/* ---- hash to curve (RFC 9380 suites *_XMD:SHA-*_SSWU_RO_) ------------------------------------------------------
+/* VerifyingKey::verify_prehash as a whole (k256/src/schnorr/verifying.rs:62-93): prehash holds n 32-byte message digests; one
+ * kernel computes the challenges e = SHA256(t || t || r || P.x || m), t = SHA256("BIP0340/challenge") (k256/src/schnorr.rs:180-186;
+ * the state after t || t is a constant of the kernel), then the call proceeds as ecgpu_schnorr_verify_batch on them.  secp256k1
+ * only: other curves give ECGPU_ERR_UNSUPPORTED. */
+int ecgpu_schnorr_verify_prehash_batch(ecgpu_ctx* ctx, int curve, const uint8_t* pubkeys_x, const uint8_t* sig_rs,
+                                       const uint8_t* prehash, uint8_t* ok, size_t n, int mem);
+
+/* ---- hash to curve (RFC 9380 suites *_XMD:SHA-*_SSWU_RO_ / _NU_) ------------------------------------------------
  * MapToCurve::map_to_curve and the sum of GroupDigest::hash_from_bytes (k256|p256|p384/src/arithmetic/hash2curve.rs):
- * u holds n x count field elements (canonical big-endian, already reduced: hash_to_field / FromOkm is host glue);
+ * u holds n x count field elements (canonical big-endian, already reduced: ecgpu_hash_to_curve_batch below starts from the
+ * message bytes instead and runs hash_to_field on the device as well);
  * count = 1: out[i] = map_to_curve(u[i]);  count = 2: out[i] = map_to_curve(u[2i]) + map_to_curve(u[2i+1]). */
 int ecgpu_map_to_curve_batch(ecgpu_ctx* ctx, int curve, const uint8_t* u, int count, uint8_t* out_xy,
                              uint8_t* out_inf, size_t n, int mem);
+
+/* The byte side of the same suites, on the device: SHA-256 / SHA-384, expand_message_xmd and FromOkm (csrc/sha2.hpp,
+ * csrc/h2c_hash.hpp).
+ * Messages: n records of msg_stride bytes; msg_len (optional, n x uint32, each <= msg_stride) makes the batch ragged, NULL =
+ * every message is msg_stride bytes (msg_stride may be 0, and msgs NULL then).  A msg_len[i] above msg_stride is refused with
+ * ECGPU_ERR_ARG for host buffers; for device buffers it is a precondition (the kernels read at most msg_stride bytes of a record).
+ * Records may have any alignment; msg_len is 4-byte aligned.
+ * dst: the domain separation tag, HOST memory whatever `mem` says, 1 .. 255 bytes: dst_len = 0 is refused like the reference's
+ * Err, and so is dst_len > 255 - the RFC's rehash of an oversize DST ("H2C-OVERSIZE-DST-") is not implemented.  It travels to
+ * the kernels in their argument block.
+ * Constant time in the messages: no branch and no address depends on a message byte; the lengths are public. */
+typedef enum ecgpu_hash { ECGPU_SHA256 = 0, ECGPU_SHA384 = 1 } ecgpu_hash;
+enum {
+  ECGPU_H2C_RO = 0, /* hash_from_bytes: two maps and their sum */
+  ECGPU_H2C_NU = 1  /* encode_from_bytes: one map */
+};
+/* ExpandMsgXmd::expand_message (external elliptic-curve crate, hash2curve/hash2field/expand_msg/xmd.rs; RFC 9380 5.3.1):
+ * out[i] = out_bytes uniform bytes of message i, 1 <= out_bytes <= 255 digests (8160 for SHA-256, 12240 for SHA-384). */
+int ecgpu_expand_message_xmd_batch(ecgpu_ctx* ctx, int hash, const uint8_t* msgs, size_t msg_stride, const uint32_t* msg_len,
+                                   const uint8_t* dst, size_t dst_len, uint8_t* out, size_t out_bytes, size_t n, int mem);
+/* FromOkm for FieldElement (k256|p256|p384/src/arithmetic/hash2curve.rs: from_okm): okm = n big-endian records of L bytes
+ * (48 for k256 / p256, 72 for p384, any alignment), out[i] = okm[i] mod p, canonical. */
+int ecgpu_field_from_okm_batch(ecgpu_ctx* ctx, int curve, const uint8_t* okm, uint8_t* out, size_t n, int mem);
+/* GroupDigest::hash_from_bytes (mode ECGPU_H2C_RO) / encode_from_bytes (ECGPU_H2C_NU) with one message and one DST per element,
+ * on the curve's own hash (SHA-256 for k256 / p256, SHA-384 for p384): one kernel runs expand_message_xmd and FromOkm and
+ * leaves the field elements in the context's workspace, the kernel of ecgpu_map_to_curve_batch maps them (count 2 / 1).
+ * out_inf may be NULL. */
+int ecgpu_hash_to_curve_batch(ecgpu_ctx* ctx, int curve, const uint8_t* msgs, size_t msg_stride, const uint32_t* msg_len,
+                              const uint8_t* dst, size_t dst_len, int mode, uint8_t* out_xy, uint8_t* out_inf, size_t n, int mem);
+/* GroupDigest::hash_to_scalar: expand_message_xmd to L bytes, then FromOkm for Scalar (= ecgpu_scalar_reduce_batch with
+ * in_bytes = L).  It derives secret keys (VOPRF DeriveKeyPair: the reference's tests, p256 hash2curve.rs:245-301), so the
+ * staged messages and scalars are cleared before the call returns and the uniform bytes do not stay in the workspace. */
+int ecgpu_hash_to_scalar_batch(ecgpu_ctx* ctx, int curve, const uint8_t* msgs, size_t msg_stride, const uint32_t* msg_len,
+                               const uint8_t* dst, size_t dst_len, uint8_t* out, size_t n, int mem);
 
 /* ---- device groups: one call, several GPUs -------------------------------------------------------------------------------
  * The reference's bulk entry points are single calls over slices (LinearCombinationExt::lincomb_ext, k256 mul.rs:325-340; `&P * &k`

@@ -8,6 +8,7 @@
 #include "sec1_kernels.hpp"
 #include "schnorr_kernels.hpp"
 #include "h2c_kernels.hpp"
+#include "h2c_hash.hpp"
 #include "straus.hpp"
 #include "scalar_ops.hpp"
 // Results per lane that share one inversion in the wide fixed-base kernels.  With only 12-16 additions per result
@@ -512,10 +513,34 @@ struct CurveOps {
     HIPCHK(c, hipGetLastError());
     return 0;
   }
+  // hash layer (h2c_hash.hpp): one message per lane
+  static int h2c_hash_to_field(ecgpu_ctx* c, const uint8_t* msgs, size_t msg_stride, const u32* msg_len, const h2c::XmdTail& tail, int count, u32* u, size_t n) {
+    const unsigned g = ecgpu_grid_for(c, n, 8);
+    if (count == 2)
+      hipLaunchKernelGGL((h2c::hash_to_field_kernel<C, 2>), dim3(g), dim3(256), 0, c->stream, msgs, msg_stride, msg_len, tail, u, n);
+    else
+      hipLaunchKernelGGL((h2c::hash_to_field_kernel<C, 1>), dim3(g), dim3(256), 0, c->stream, msgs, msg_stride, msg_len, tail, u, n);
+    HIPCHK(c, hipGetLastError());
+    return 0;
+  }
+  static int field_from_okm(ecgpu_ctx* c, const uint8_t* okm, u32* out, size_t n) {
+    hipLaunchKernelGGL((h2c::field_from_okm_kernel<C>), dim3(ecgpu_grid_for(c, n, 8)), dim3(256), 0, c->stream, okm, out, n);
+    HIPCHK(c, hipGetLastError());
+    return 0;
+  }
+  static int schnorr_challenge(ecgpu_ctx* c, const u32* px, const u32* sig, const u32* prehash, u32* e, size_t n) {
+    if constexpr (C::ID != 0) {
+      return ecgpu_set_err(c, ECGPU_ERR_UNSUPPORTED, "ecgpu_schnorr_verify_prehash_batch: BIP340 is defined over secp256k1 only");
+    } else {
+      hipLaunchKernelGGL((h2c::bip340_challenge_kernel<0>), dim3(ecgpu_grid_for(c, n, 8)), dim3(256), 0, c->stream, px, sig, prehash, e, n);
+      HIPCHK(c, hipGetLastError());
+      return 0;
+    }
+  }
   static const ecgpu_curve_ops* table() {
     static const ecgpu_curve_ops t = {field_op, point_op, point_eq, normalize, lincomb, msm, validate_scalars, validate_points,
                                       decompress, synth_scalars, synth_points, to_bytes, from_bytes, sec1_encode, sec1_decode, ecdsa_verify, h2c_map, ecdsa_recover, schnorr_verify, ecdsa_sign, ecdh,
-                                      pass_units, scalar_op, scalar_reduce};
+                                      pass_units, scalar_op, scalar_reduce, h2c_hash_to_field, field_from_okm, schnorr_challenge};
     return &t;
   }
 };

@@ -170,7 +170,7 @@ static const ecgpu_curve_ops* ops_for(int curve) {
 
 extern "C" {
 
-const char* ecgpu_version(void) { return "ecgpu 0.5 (gfx950)"; }
+const char* ecgpu_version(void) { return "ecgpu 0.6 (gfx950)"; }
 
 size_t ecgpu_field_bytes(int curve) {
   switch (curve) {
@@ -228,7 +228,7 @@ void ecgpu_destroy(ecgpu_ctx* c) {
   for (auto& kind : c->table)
     for (void* t : kind)
       if (t) (void)hipFree(t);
-  for (DevBuf* b : {&c->msm_ws, &c->tab_ws, &c->ecdsa_ws})
+  for (DevBuf* b : {&c->msm_ws, &c->tab_ws, &c->ecdsa_ws, &c->hash_ws})
     if (b->p) (void)hipFree(b->p);
   if (c->sched_ctr) (void)hipFree(c->sched_ctr);
   if (c->ev0) (void)hipEventDestroy(c->ev0);
@@ -334,6 +334,7 @@ int ecgpu_debug_workspace(ecgpu_ctx* c, int which, void* host_copy, size_t cap, 
   if (which == 0) ws = &c->tab_ws;
   else if (which == 1) ws = &c->ecdsa_ws;
   else if (which == 2) ws = &c->msm_ws;
+  else if (which == 3) ws = &c->hash_ws;
   else if (which >= 16 && which < 16 + ecgpu_ctx::NSTAGE) ws = &c->stage[which - 16];
   else return ecgpu_set_err(c, ECGPU_ERR_ARG, "ecgpu_debug_workspace: unknown workspace %d", which);
   void* p = ws->p;
@@ -689,6 +690,113 @@ int ecgpu_ecdh_batch(ecgpu_ctx* c, int curve, const uint8_t* secret_d, const uin
   const CallArg args[] = {arg_in(secret_d, nb, ARG_SECRET), arg_in(pubkeys_xy, 2 * nb), arg_out(shared_x, nb, ARG_SECRET), arg_out(ok, 1)};
   return run_batch(c, mem, n, args, ops->pass_units(c, 1, 1, ECGPU_SECRET_SCALARS), [&](void** d, size_t cnt) {
     return ops->ecdh(c, (const uint32_t*)d[0], (const uint32_t*)d[1], (uint32_t*)d[2], (uint8_t*)d[3], cnt);
+  });
+}
+
+// ---------------------------------------------------------------------------------------------
+// hash layer (h2c_hash.hpp): everything that starts from message bytes.  The messages of a call share one DST, which travels in the
+// kernels' argument block (XmdTail); msg_len is the optional per-message length.
+// ---------------------------------------------------------------------------------------------
+// the checks every call over messages and a DST makes; fills `tail` for out_len uniform bytes per message
+static int xmd_enter(ecgpu_ctx* c, const uint8_t* msgs, size_t msg_stride, const uint32_t* msg_len, const uint8_t* dst, size_t dst_len, size_t out_len,
+                     size_t n, int mem, ecgpu::h2c::XmdTail& tail) {
+  if (dst_len == 0) return ecgpu_set_err(c, ECGPU_ERR_ARG, "expand_message_xmd: the DST is empty");
+  if (!dst || (msg_stride && !msgs)) return ecgpu_set_err(c, ECGPU_ERR_ARG, "null argument");
+  if (dst_len > 255) return ecgpu_set_err(c, ECGPU_ERR_ARG, "expand_message_xmd: DST of %zu bytes (above 255 the RFC rehashes it: not implemented)", dst_len);
+  if (msg_stride > 0xFFFFFFFFu) return ecgpu_set_err(c, ECGPU_ERR_ARG, "msg_stride %zu does not fit 32 bits", msg_stride);
+  if (msg_len && mem == ECGPU_MEM_HOST)
+    for (size_t i = 0; i < n; i++)
+      if (msg_len[i] > msg_stride) return ecgpu_set_err(c, ECGPU_ERR_ARG, "msg_len[%zu] = %u is above msg_stride = %zu", i, msg_len[i], msg_stride);
+  ecgpu::h2c::xmd_tail_set(tail, dst, dst_len, out_len);
+  return 0;
+}
+static size_t okm_bytes(int curve) { return curve == ECGPU_P384 ? 72 : 48; }               // FromOkm::Length
+static int curve_hash(int curve) { return curve == ECGPU_P384 ? ECGPU_SHA384 : ECGPU_SHA256; }
+
+int ecgpu_expand_message_xmd_batch(ecgpu_ctx* c, int hash, const uint8_t* msgs, size_t msg_stride, const uint32_t* msg_len, const uint8_t* dst,
+                                   size_t dst_len, uint8_t* out, size_t out_bytes, size_t n, int mem) {
+  if (!c || !out) return ecgpu_set_err(c, ECGPU_ERR_ARG, "null argument");
+  if (hash != ECGPU_SHA256 && hash != ECGPU_SHA384) return ecgpu_set_err(c, ECGPU_ERR_ARG, "unknown hash %d", hash);
+  const size_t digest = hash == ECGPU_SHA384 ? 48 : 32;
+  if (out_bytes < 1 || out_bytes > 255 * digest) return ecgpu_set_err(c, ECGPU_ERR_ARG, "out_bytes %zu outside 1 .. %zu (255 digests)", out_bytes, 255 * digest);
+  ecgpu::h2c::XmdTail tail;
+  int rc = xmd_enter(c, msgs, msg_stride, msg_len, dst, dst_len, out_bytes, n, mem, tail);
+  if (rc) return rc;
+  if (n == 0) return ECGPU_OK;
+  std::lock_guard<std::mutex> lk(c->mu);
+  HIPCHK(c, hipSetDevice(c->device));
+  const CallArg args[] = {arg_in(msg_stride ? msgs : nullptr, msg_stride, ARG_OPTIONAL), arg_in(msg_len, 4, ARG_OPTIONAL), arg_out(out, out_bytes)};
+  return run_batch(c, mem, n, args, (size_t)1 << 22, [&](void** d, size_t cnt) {
+    return ecgpuint_xmd(c, hash, (const uint8_t*)d[0], msg_stride, (const uint32_t*)d[1], tail, (uint8_t*)d[2], cnt);
+  });
+}
+int ecgpu_field_from_okm_batch(ecgpu_ctx* c, int curve, const uint8_t* okm, uint8_t* out, size_t n, int mem) {
+  if (!c || !okm || !out) return ecgpu_set_err(c, ECGPU_ERR_ARG, "null argument");
+  if (n == 0) return ECGPU_OK;
+  ENTER(c, curve);
+  const CallArg args[] = {arg_in(okm, okm_bytes(curve)), arg_out(out, nb)};
+  return run_batch(c, mem, n, args, (size_t)1 << 22, [&](void** d, size_t cnt) { return ops->field_from_okm(c, (const uint8_t*)d[0], (uint32_t*)d[1], cnt); });
+}
+int ecgpu_hash_to_curve_batch(ecgpu_ctx* c, int curve, const uint8_t* msgs, size_t msg_stride, const uint32_t* msg_len, const uint8_t* dst, size_t dst_len,
+                              int mode, uint8_t* out_xy, uint8_t* out_inf, size_t n, int mem) {
+  if (!c || !out_xy) return ecgpu_set_err(c, ECGPU_ERR_ARG, "null argument");
+  if (mode != ECGPU_H2C_RO && mode != ECGPU_H2C_NU) return ecgpu_set_err(c, ECGPU_ERR_ARG, "unknown hash-to-curve mode %d", mode);
+  if (!ecgpu_field_bytes(curve)) return ecgpu_set_err(c, ECGPU_ERR_UNSUPPORTED, "curve %d not supported", curve);
+  const int count = mode == ECGPU_H2C_RO ? 2 : 1;
+  ecgpu::h2c::XmdTail tail;
+  int rc = xmd_enter(c, msgs, msg_stride, msg_len, dst, dst_len, count * okm_bytes(curve), n, mem, tail);
+  if (rc) return rc;
+  if (n == 0) return ECGPU_OK;
+  ENTER(c, curve);
+  const CallArg args[] = {arg_in(msg_stride ? msgs : nullptr, msg_stride, ARG_OPTIONAL), arg_in(msg_len, 4, ARG_OPTIONAL), arg_out(out_xy, 2 * nb),
+                          arg_out(out_inf, 1, ARG_OPTIONAL)};
+  return run_batch(c, mem, n, args, (size_t)1 << 22, [&](void** d, size_t cnt) {
+    // the field elements go through the pipeline workspace (ecgpu_debug_workspace 1) in the layout the map kernel reads
+    int r = ecgpu_reserve(c, c->ecdsa_ws, cnt * count * nb);
+    if (r) return r;
+    uint32_t* u = (uint32_t*)c->ecdsa_ws.p;
+    if ((r = ops->h2c_hash_to_field(c, (const uint8_t*)d[0], msg_stride, (const uint32_t*)d[1], tail, count, u, cnt))) return r;
+    return ops->h2c_map(c, u, count, (uint32_t*)d[2], (uint8_t*)d[3], cnt);
+  });
+}
+// derives secret keys: the staged messages and scalars are cleared on every exit path, and so are the uniform bytes in the workspace
+int ecgpu_hash_to_scalar_batch(ecgpu_ctx* c, int curve, const uint8_t* msgs, size_t msg_stride, const uint32_t* msg_len, const uint8_t* dst, size_t dst_len,
+                               uint8_t* out, size_t n, int mem) {
+  if (!c || !out) return ecgpu_set_err(c, ECGPU_ERR_ARG, "null argument");
+  if (!ecgpu_field_bytes(curve)) return ecgpu_set_err(c, ECGPU_ERR_UNSUPPORTED, "curve %d not supported", curve);
+  const size_t L = okm_bytes(curve);
+  ecgpu::h2c::XmdTail tail;
+  int rc = xmd_enter(c, msgs, msg_stride, msg_len, dst, dst_len, L, n, mem, tail);
+  if (rc) return rc;
+  if (n == 0) return ECGPU_OK;
+  ENTER(c, curve);
+  const CallArg args[] = {arg_in(msg_stride ? msgs : nullptr, msg_stride, ARG_SECRET | ARG_OPTIONAL), arg_in(msg_len, 4, ARG_OPTIONAL), arg_out(out, nb, ARG_SECRET)};
+  return run_batch(c, mem, n, args, (size_t)1 << 22, [&](void** d, size_t cnt) {
+    int r = ecgpu_reserve(c, c->ecdsa_ws, cnt * L);
+    if (r) return r;
+    uint8_t* okm = (uint8_t*)c->ecdsa_ws.p;
+    struct OkmWipe {
+      ecgpu_ctx* c; void* p; size_t b;
+      ~OkmWipe() { (void)hipMemsetAsync(p, 0, b, c->stream); }
+    } okm_wipe{c, okm, cnt * L};
+    if ((r = ecgpuint_xmd(c, curve_hash(curve), (const uint8_t*)d[0], msg_stride, (const uint32_t*)d[1], tail, okm, cnt))) return r;
+    return ops->scalar_reduce(c, okm, L, (uint32_t*)d[2], cnt, 0);
+  });
+}
+int ecgpu_schnorr_verify_prehash_batch(ecgpu_ctx* c, int curve, const uint8_t* pubkeys_x, const uint8_t* sig_rs, const uint8_t* prehash, uint8_t* ok,
+                                       size_t n, int mem) {
+  if (!c || !pubkeys_x || !sig_rs || !prehash || !ok) return ecgpu_set_err(c, ECGPU_ERR_ARG, "null argument");
+  if (ecgpu_field_bytes(curve) && curve != ECGPU_K256)
+    return ecgpu_set_err(c, ECGPU_ERR_UNSUPPORTED, "ecgpu_schnorr_verify_prehash_batch: BIP340 is defined over secp256k1 only");
+  if (n == 0) return ECGPU_OK;
+  ENTER(c, curve);
+  const CallArg args[] = {arg_in(pubkeys_x, nb), arg_in(sig_rs, 2 * nb), arg_in(prehash, 32), arg_out(ok, 1)};
+  return run_batch(c, mem, n, args, ops->pass_units(c, 1, 1, 0), [&](void** d, size_t cnt) {
+    int r = ecgpu_reserve(c, c->hash_ws, cnt * 32);
+    if (r) return r;
+    uint32_t* e = (uint32_t*)c->hash_ws.p;
+    if ((r = ops->schnorr_challenge(c, (const uint32_t*)d[0], (const uint32_t*)d[1], (const uint32_t*)d[2], e, cnt))) return r;
+    return ops->schnorr_verify(c, (const uint32_t*)d[0], (const uint32_t*)d[1], e, (uint8_t*)d[3], cnt);
   });
 }
 

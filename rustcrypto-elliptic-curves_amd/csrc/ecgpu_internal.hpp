@@ -9,6 +9,7 @@
 #include <mutex>
 
 #include "../../include/ecgpu.h"
+#include "xmd_tail.hpp"
 
 // A grow-only device buffer (ecgpu_reserve below): scratch whose contents do not survive growing.
 struct DevBuf {
@@ -65,6 +66,9 @@ struct ecgpu_ctx {
   unsigned sched_next = 0;
   // intermediate scalars / points of the ECDSA pipelines (grow-only)
   DevBuf ecdsa_ws;
+  // BIP340 challenges of ecgpu_schnorr_verify_prehash_batch (grow-only): they live through the verification pipeline, which lays
+  // out ecdsa_ws for itself
+  DevBuf hash_ws;
 };
 
 static inline int ecgpu_set_err(ecgpu_ctx* c, int code, const char* fmt, ...) {
@@ -164,7 +168,16 @@ struct ecgpu_curve_ops {
   // scalar field (scalar_ops.hpp): canonical big-endian scalars in and out; ok may be NULL
   int (*scalar_op)(ecgpu_ctx* c, int op, const uint32_t* a, const uint32_t* b, uint32_t* out, uint8_t* ok, size_t n);
   int (*scalar_reduce)(ecgpu_ctx* c, const uint8_t* in, size_t in_bytes, uint32_t* out, size_t n, unsigned flags);
+  // hash layer (h2c_hash.hpp).  h2c_hash_to_field: expand_message_xmd on the curve's hash fused with FromOkm, u = n x count field
+  // elements as h2c_map reads them (msg_len may be NULL; tail.out_len = count L); field_from_okm: n records of L bytes -> n field
+  // elements; schnorr_challenge: e = n BIP340 challenge hashes (secp256k1 only)
+  int (*h2c_hash_to_field)(ecgpu_ctx* c, const uint8_t* msgs, size_t msg_stride, const uint32_t* msg_len, const ecgpu::h2c::XmdTail& tail, int count,
+                           uint32_t* u, size_t n);
+  int (*field_from_okm)(ecgpu_ctx* c, const uint8_t* okm, uint32_t* out, size_t n);
+  int (*schnorr_challenge)(ecgpu_ctx* c, const uint32_t* px, const uint32_t* sig, const uint32_t* prehash, uint32_t* e, size_t n);
 };
+// expand_message_xmd to raw bytes on `hash` (ecgpu_hash), curve-independent (h2c_hash.hip): out = n x tail.out_len bytes
+int ecgpuint_xmd(ecgpu_ctx* c, int hash, const uint8_t* msgs, size_t msg_stride, const uint32_t* msg_len, const ecgpu::h2c::XmdTail& tail, uint8_t* out, size_t n);
 // Pippenger MSM, one translation unit per curve (msm_*.hip); `mul` is the curve's batch scalar multiplication (affine in / out
 // on device memory), used for small sums
 typedef int (*ecgpu_msm_mul_fn)(ecgpu_ctx* c, const uint32_t* scalars, const uint32_t* points, int pt_fmt, uint32_t* out_xy, size_t n);

@@ -1,6 +1,7 @@
 // BIP340 Schnorr verification for batches: the elliptic-curve part of
 // `VerifyingKey::verify_prehash` (k256/src/schnorr/verifying.rs:62-93).
-//   e = tagged_hash("BIP0340/challenge", r || P.x || m) mod n is computed by the caller (SHA-256 is host-side glue);
+//   e = tagged_hash("BIP0340/challenge", r || P.x || m) mod n comes from the caller (ecgpu_schnorr_verify_batch) or from the
+//   challenge kernel of h2c_hash.hpp (ecgpu_schnorr_verify_prehash_batch);
 //   R = s G + (-e) P must be finite, have even y and x(R) = r.
 // Pipeline: verify_prep (decode r, s, lift_x of the key, -e) -> fixed-base kernel (s G) -> variable-base kernel
 // ((-e) P) -> verify_check (affine sum with one inversion per BATCH signatures, parity and x tests).

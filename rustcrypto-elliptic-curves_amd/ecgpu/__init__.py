@@ -36,6 +36,11 @@ FE_MUL, FE_SQR, FE_ADD, FE_SUB, FE_NEG, FE_INV, FE_SQRT = range(7)
 SC_MUL, SC_SQR, SC_ADD, SC_SUB, SC_NEG, SC_INV, SC_SQRT = range(7)      # ecgpu_scalar_op
 SC_BINARY = (SC_MUL, SC_ADD, SC_SUB)
 REDUCE_NONZERO = 1
+SHA256, SHA384 = 0, 1                                                  # ecgpu_hash
+H2C_RO, H2C_NU = 0, 1                                                  # hash_from_bytes / encode_from_bytes
+CURVE_HASH = {K256: SHA256, P256: SHA256, P384: SHA384}                # the hash of the curve's RFC 9380 suite
+OKM_BYTES = {K256: 48, P256: 48, P384: 72}                             # FromOkm::Length
+DIGEST_BYTES = {SHA256: 32, SHA384: 48}
 # ecgpu_option (per-context tuning / test knobs, include/ecgpu.h)
 OPT_FB_WINDOW, OPT_FB_MAX_WINDOW, OPT_MSM_WINDOW_BITS, OPT_MSM_SLAB_TERMS, OPT_MSM_SMALL_PATH, OPT_MSM_ROUNDS, OPT_K256_WAVES, OPT_FB_MEMORY_BUDGET, OPT_LINCOMB_TERM_BY_TERM = range(9)
 
@@ -143,6 +148,11 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
     lib.ecgpu_map_to_curve_batch.argtypes = [vp, i, u8p, i, u8p, u8p, sz, i]
     lib.ecgpu_ecdsa_recover_batch.argtypes = [vp, i, u8p, u8p, u8p, u8p, u8p, sz, i, ctypes.c_uint]
     lib.ecgpu_schnorr_verify_batch.argtypes = [vp, i, u8p, u8p, u8p, u8p, sz, i]
+    lib.ecgpu_schnorr_verify_prehash_batch.argtypes = [vp, i, u8p, u8p, u8p, u8p, sz, i]
+    lib.ecgpu_expand_message_xmd_batch.argtypes = [vp, i, u8p, sz, u8p, u8p, sz, u8p, sz, sz, i]
+    lib.ecgpu_field_from_okm_batch.argtypes = [vp, i, u8p, u8p, sz, i]
+    lib.ecgpu_hash_to_curve_batch.argtypes = [vp, i, u8p, sz, u8p, u8p, sz, i, u8p, u8p, sz, i]
+    lib.ecgpu_hash_to_scalar_batch.argtypes = [vp, i, u8p, sz, u8p, u8p, sz, u8p, sz, i]
     lib.ecgpu_ecdsa_sign_batch.argtypes = [vp, i, u8p, u8p, u8p, u8p, u8p, u8p, sz, i, ctypes.c_uint]
     lib.ecgpu_synth_scalars.argtypes = [vp, i, ctypes.c_uint64, ctypes.c_uint64, u8p, sz]
     lib.ecgpu_synth_points.argtypes = [vp, i, ctypes.c_uint64, ctypes.c_uint64, u8p, sz]
@@ -157,7 +167,8 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
                  "ecgpu_set_option", "ecgpu_get_option", "ecgpu_fb_table_bytes", "ecgpu_sec1_encode_batch", "ecgpu_sec1_decode_batch",
                  "ecgpu_ecdh_batch", "ecgpu_debug_workspace", "ecgpu_host_chunk_schedule", "ecgpu_group_create", "ecgpu_group_size",
                  "ecgpu_group_synchronize", "ecgpu_shard_range", "ecgpu_group_mul_batch", "ecgpu_group_lincomb_batch", "ecgpu_group_lincomb_sharded",
-                 "ecgpu_group_msm", "ecgpu_group_msm_sharded"):
+                 "ecgpu_group_msm", "ecgpu_group_msm_sharded", "ecgpu_schnorr_verify_prehash_batch", "ecgpu_expand_message_xmd_batch",
+                 "ecgpu_field_from_okm_batch", "ecgpu_hash_to_curve_batch", "ecgpu_hash_to_scalar_batch"):
         getattr(lib, name).restype = ctypes.c_int
     if path is None:
         _lib = lib
@@ -177,6 +188,8 @@ EXPORTED_SYMBOLS = (
     "ecgpu_group_create", "ecgpu_group_destroy", "ecgpu_group_size", "ecgpu_group_context", "ecgpu_group_last_error", "ecgpu_group_gather_path",
     "ecgpu_group_synchronize", "ecgpu_shard_range", "ecgpu_group_mul_batch", "ecgpu_group_lincomb_batch", "ecgpu_group_lincomb_sharded",
     "ecgpu_group_msm", "ecgpu_group_msm_sharded",
+    "ecgpu_schnorr_verify_prehash_batch", "ecgpu_expand_message_xmd_batch", "ecgpu_field_from_okm_batch", "ecgpu_hash_to_curve_batch",
+    "ecgpu_hash_to_scalar_batch",
 )
 
 
@@ -304,6 +317,30 @@ def _as_host(x, width: int) -> np.ndarray:
     else:
         a = np.frombuffer(b"".join(x), dtype=np.uint8).reshape(-1, width).copy()
     return a
+
+
+def pack_messages(msgs: Sequence[bytes], stride: Optional[int] = None):
+    """list of byte strings -> (records (n, stride) uint8, lengths (n,) uint32, stride): the ragged-batch form of the hash entry
+    points.  stride defaults to the longest message."""
+    lens = np.array([len(m) for m in msgs], dtype=np.uint32)
+    if stride is None:
+        stride = int(lens.max()) if len(msgs) else 0
+    if len(msgs) and int(lens.max()) > stride:
+        raise ValueError("a message is longer than the stride (%d > %d)" % (int(lens.max()), stride))
+    rec = np.zeros((len(msgs), stride), dtype=np.uint8)
+    for k, m in enumerate(msgs):
+        rec[k, :len(m)] = np.frombuffer(m, dtype=np.uint8)
+    return rec, lens, stride
+
+
+def expand_message_xmd(ctx: "Context", hash_id: int, msgs: Sequence[bytes], dst: bytes, out_bytes: int) -> np.ndarray:
+    """ExpandMsgXmd::expand_message for a batch on the device -> (n, out_bytes) uniform bytes (ecgpu_expand_message_xmd_batch)"""
+    rec, lens, stride = pack_messages(msgs)
+    out = _host_out(len(msgs), out_bytes)
+    d = np.frombuffer(bytes(dst), dtype=np.uint8)
+    ctx.check(ctx.lib.ecgpu_expand_message_xmd_batch(ctx.handle, hash_id, _ptr(rec)[0] if stride else None, stride, _ptr(lens)[0], _ptr(d)[0] if len(d) else None,
+                                                     len(d), _ptr(out)[0], out_bytes, len(msgs), HOST))
+    return out
 
 
 class Curve:
@@ -575,6 +612,46 @@ class Curve:
         out, inf = _host_out(n, 2 * self.nb), np.zeros(n, dtype=np.uint8)
         self.ctx.check(self.ctx.lib.ecgpu_map_to_curve_batch(self.ctx.handle, self.id, _ptr(uu)[0], count, _ptr(out)[0], _ptr(inf)[0], n, HOST))
         return out, inf
+
+    # --- GroupDigest / FromOkm: everything that starts from bytes (SHA-2, expand_message_xmd and the reductions run on the device)
+    def hash_to_curve(self, msgs: Sequence[bytes], dst: bytes, mode: int = H2C_RO):
+        """GroupDigest::hash_from_bytes (H2C_RO) / encode_from_bytes (H2C_NU), one message per element -> (points_xy, inf)"""
+        rec, lens, stride = pack_messages(msgs)
+        n = len(msgs)
+        out, inf = _host_out(n, 2 * self.nb), np.zeros(n, dtype=np.uint8)
+        d = np.frombuffer(bytes(dst), dtype=np.uint8)
+        self.ctx.check(self.ctx.lib.ecgpu_hash_to_curve_batch(self.ctx.handle, self.id, _ptr(rec)[0] if stride else None, stride, _ptr(lens)[0],
+                                                              _ptr(d)[0] if len(d) else None, len(d), mode, _ptr(out)[0], _ptr(inf)[0], n, HOST))
+        return out, inf
+
+    def hash_to_scalar(self, msgs: Sequence[bytes], dst: bytes) -> np.ndarray:
+        """GroupDigest::hash_to_scalar -> (n, NB) canonical scalars"""
+        rec, lens, stride = pack_messages(msgs)
+        out = _host_out(len(msgs), self.nb)
+        d = np.frombuffer(bytes(dst), dtype=np.uint8)
+        self.ctx.check(self.ctx.lib.ecgpu_hash_to_scalar_batch(self.ctx.handle, self.id, _ptr(rec)[0] if stride else None, stride, _ptr(lens)[0],
+                                                               _ptr(d)[0] if len(d) else None, len(d), _ptr(out)[0], len(msgs), HOST))
+        return out
+
+    def field_from_okm(self, okm) -> np.ndarray:
+        """FromOkm for FieldElement: big-endian records of L bytes (48, p384: 72) -> canonical field elements okm mod p"""
+        o = _as_host(okm, OKM_BYTES[self.id])
+        out = _host_out(len(o), self.nb)
+        self.ctx.check(self.ctx.lib.ecgpu_field_from_okm_batch(self.ctx.handle, self.id, _ptr(o)[0], _ptr(out)[0], len(o), HOST))
+        return out
+
+    def expand_message_xmd(self, msgs: Sequence[bytes], dst: bytes, out_bytes: int) -> np.ndarray:
+        """expand_message_xmd on the curve's own hash"""
+        return expand_message_xmd(self.ctx, CURVE_HASH[self.id], msgs, dst, out_bytes)
+
+    def schnorr_verify_prehash(self, pubkeys_x, sig_rs, prehashes) -> np.ndarray:
+        """VerifyingKey::verify_prehash for a batch: the BIP340 challenge hashes are computed on the device as well"""
+        x, sg, m = _as_host(pubkeys_x, self.nb), _as_host(sig_rs, 2 * self.nb), _as_host(prehashes, 32)
+        if not (len(x) == len(sg) == len(m)):
+            raise ValueError("key, signature and prehash batches differ in length")
+        ok = np.zeros(len(x), dtype=np.uint8)
+        self.ctx.check(self.ctx.lib.ecgpu_schnorr_verify_prehash_batch(self.ctx.handle, self.id, _ptr(x)[0], _ptr(sg)[0], _ptr(m)[0], _ptr(ok)[0], len(x), HOST))
+        return ok
 
     def ecdsa_recover(self, prehash, sig_rs, recovery_id, flags: Optional[int] = None):
         """VerifyingKey::recover_from_prehash for a batch -> (pubkeys_xy, ok)"""

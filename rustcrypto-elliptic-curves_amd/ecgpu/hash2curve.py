@@ -1,7 +1,9 @@
 """GroupDigest::hash_from_bytes for batches (RFC 9380 *_XMD:SHA-*_SSWU_RO_ suites of k256 / p256 / p384).
 
-Host: expand_message_xmd and hash_to_field (SHA-2 and a reduction mod p per element - byte glue).  Device: the two
-map_to_curve evaluations and their sum (`Curve.map_to_curve`, ecgpu_map_to_curve_batch)."""
+hash_from_bytes_device runs everything on the device (`Curve.hash_to_curve`, ecgpu_hash_to_curve_batch: SHA-2,
+expand_message_xmd, FromOkm, the two maps and their sum).  The host functions below remain for callers that hold the field
+elements already, and as a cross-check: expand_message_xmd and hash_to_field over hashlib, then the device map
+(`Curve.map_to_curve`, ecgpu_map_to_curve_batch)."""
 from __future__ import annotations
 
 import hashlib
@@ -42,3 +44,8 @@ def hash_from_bytes(curve: Curve, msgs: Sequence[bytes], dst: bytes):
     """-> (points_xy, inf): one curve point per message."""
     u = b"".join(hash_to_field(curve, m, dst, 2) for m in msgs)
     return curve.map_to_curve(u, count=2)
+
+
+def hash_from_bytes_device(curve: Curve, msgs: Sequence[bytes], dst: bytes):
+    """-> (points_xy, inf): one curve point per message, hashing included on the device."""
+    return curve.hash_to_curve(list(msgs), dst)

@@ -36,6 +36,15 @@ def verify_batch(curve: Curve, pubkeys_x: Sequence[bytes], prehashes: Sequence[b
     return curve.schnorr_verify(b"".join(pubkeys_x), b"".join(sigs), challenges(pubkeys_x, prehashes, sigs))
 
 
+def verify_batch_device(curve: Curve, pubkeys_x: Sequence[bytes], prehashes: Sequence[bytes], sigs: Sequence[bytes]) -> np.ndarray:
+    """verify_batch with the challenge hashes computed on the device too (ecgpu_schnorr_verify_prehash_batch)."""
+    if curve.id != K256:
+        raise ValueError("BIP340 is defined over secp256k1")
+    if any(len(m) != 32 for m in prehashes):
+        raise ValueError("verify_prehash takes 32-byte digests")     # verifying.rs:68
+    return curve.schnorr_verify_prehash(b"".join(pubkeys_x), b"".join(sigs), b"".join(prehashes))
+
+
 def sign_batch(curve: Curve, secret_keys: Sequence[bytes], prehashes: Sequence[bytes], aux_rands: Sequence[bytes]):
     """sign_prehash_with_aux_rand (signing.rs:80-131) for a batch -> (signatures, public keys x-only)."""
     if curve.id != K256:

@@ -46,6 +46,12 @@ pub const ECGPU_SC_INV: c_int = 5;
 pub const ECGPU_SC_SQRT: c_int = 6;
 /// `ecgpu_scalar_reduce_batch`: ReduceNonZero (int mod (n - 1) + 1) instead of Reduce (int mod n)
 pub const ECGPU_REDUCE_NONZERO: c_uint = 1;
+/// `ecgpu_hash`: the hash of `ecgpu_expand_message_xmd_batch`
+pub const ECGPU_SHA256: c_int = 0;
+pub const ECGPU_SHA384: c_int = 1;
+/// `ecgpu_hash_to_curve_batch`: hash_from_bytes (two maps and their sum) / encode_from_bytes (one map)
+pub const ECGPU_H2C_RO: c_int = 0;
+pub const ECGPU_H2C_NU: c_int = 1;
 /// the reference's own schedule, constant-time table scans included: exact (X, Y, Z), and the one for secret scalars
 pub const ECGPU_EXACT_REFERENCE: c_uint = 1;
 /// the k256 low-s rules of k256/src/ecdsa.rs:182-207
@@ -129,6 +135,15 @@ extern "C" {
     pub fn ecgpu_schnorr_verify_batch(ctx: *mut ecgpu_ctx, curve: c_int, pubkeys_x: *const u8, sig_rs: *const u8, challenges: *const u8, ok: *mut u8, n: usize,
                                       mem: c_int) -> c_int;
     pub fn ecgpu_map_to_curve_batch(ctx: *mut ecgpu_ctx, curve: c_int, u: *const u8, count: c_int, out_xy: *mut u8, out_inf: *mut u8, n: usize, mem: c_int) -> c_int;
+    pub fn ecgpu_schnorr_verify_prehash_batch(ctx: *mut ecgpu_ctx, curve: c_int, pubkeys_x: *const u8, sig_rs: *const u8, prehash: *const u8, ok: *mut u8, n: usize,
+                                              mem: c_int) -> c_int;
+    pub fn ecgpu_expand_message_xmd_batch(ctx: *mut ecgpu_ctx, hash: c_int, msgs: *const u8, msg_stride: usize, msg_len: *const u32, dst: *const u8, dst_len: usize,
+                                          out: *mut u8, out_bytes: usize, n: usize, mem: c_int) -> c_int;
+    pub fn ecgpu_field_from_okm_batch(ctx: *mut ecgpu_ctx, curve: c_int, okm: *const u8, out: *mut u8, n: usize, mem: c_int) -> c_int;
+    pub fn ecgpu_hash_to_curve_batch(ctx: *mut ecgpu_ctx, curve: c_int, msgs: *const u8, msg_stride: usize, msg_len: *const u32, dst: *const u8, dst_len: usize,
+                                     mode: c_int, out_xy: *mut u8, out_inf: *mut u8, n: usize, mem: c_int) -> c_int;
+    pub fn ecgpu_hash_to_scalar_batch(ctx: *mut ecgpu_ctx, curve: c_int, msgs: *const u8, msg_stride: usize, msg_len: *const u32, dst: *const u8, dst_len: usize,
+                                      out: *mut u8, n: usize, mem: c_int) -> c_int;
     pub fn ecgpu_group_create(group: *mut *mut ecgpu_group, devices: *const c_int, n_devices: c_int, flags: c_uint) -> c_int;
     pub fn ecgpu_group_destroy(group: *mut ecgpu_group);
     pub fn ecgpu_group_size(group: *const ecgpu_group) -> c_int;
@@ -398,6 +413,63 @@ impl Context {
         let (mut xy, mut inf) = (vec![0u8; 2 * nb * n], vec![0u8; n]);
         self.check(unsafe { ecgpu_map_to_curve_batch(self.0, curve, u.as_ptr(), count, xy.as_mut_ptr(), inf.as_mut_ptr(), n, ECGPU_MEM_HOST) })?;
         Ok((xy, inf))
+    }
+    /// byte strings -> records of one stride (the longest message) and their lengths: the ragged-batch form of the hash calls
+    fn pack_messages(msgs: &[&[u8]]) -> (Vec<u8>, Vec<u32>, usize) {
+        let stride = msgs.iter().map(|m| m.len()).max().unwrap_or(0);
+        let mut rec = vec![0u8; stride * msgs.len()];
+        for (i, m) in msgs.iter().enumerate() { rec[i * stride..i * stride + m.len()].copy_from_slice(m); }
+        (rec, msgs.iter().map(|m| m.len() as u32).collect(), stride)
+    }
+    /// ExpandMsgXmd::expand_message for a batch (hash: ECGPU_SHA256 | ECGPU_SHA384) -> out_bytes uniform bytes per message
+    pub fn expand_message_xmd(&self, hash: c_int, msgs: &[&[u8]], dst: &[u8], out_bytes: usize) -> Result<Vec<u8>, Error> {
+        let (rec, lens, stride) = Self::pack_messages(msgs);
+        let mut out = vec![0u8; out_bytes * msgs.len()];
+        self.check(unsafe {
+            ecgpu_expand_message_xmd_batch(self.0, hash, rec.as_ptr(), stride, lens.as_ptr(), dst.as_ptr(), dst.len(), out.as_mut_ptr(), out_bytes, msgs.len(), ECGPU_MEM_HOST)
+        })?;
+        Ok(out)
+    }
+    /// FromOkm for FieldElement: records of 48 (p384: 72) bytes -> canonical field elements
+    pub fn field_from_okm(&self, curve: c_int, okm: &[u8]) -> Result<Vec<u8>, Error> {
+        let nb = Self::field_bytes(curve);
+        let l = if curve == ECGPU_P384 { 72 } else { 48 };
+        Self::arg(nb != 0 && okm.len() % l == 0)?;
+        let mut out = vec![0u8; nb * (okm.len() / l)];
+        self.check(unsafe { ecgpu_field_from_okm_batch(self.0, curve, okm.as_ptr(), out.as_mut_ptr(), okm.len() / l, ECGPU_MEM_HOST) })?;
+        Ok(out)
+    }
+    /// GroupDigest::hash_from_bytes (ECGPU_H2C_RO) / encode_from_bytes (ECGPU_H2C_NU), one message per element -> (x || y, infinity flags)
+    pub fn hash_to_curve(&self, curve: c_int, msgs: &[&[u8]], dst: &[u8], mode: c_int) -> Result<(Vec<u8>, Vec<u8>), Error> {
+        let nb = Self::field_bytes(curve);
+        Self::arg(nb != 0)?;
+        let (rec, lens, stride) = Self::pack_messages(msgs);
+        let (mut xy, mut inf) = (vec![0u8; 2 * nb * msgs.len()], vec![0u8; msgs.len()]);
+        self.check(unsafe {
+            ecgpu_hash_to_curve_batch(self.0, curve, rec.as_ptr(), stride, lens.as_ptr(), dst.as_ptr(), dst.len(), mode, xy.as_mut_ptr(), inf.as_mut_ptr(), msgs.len(),
+                                      ECGPU_MEM_HOST)
+        })?;
+        Ok((xy, inf))
+    }
+    /// GroupDigest::hash_to_scalar -> canonical scalars (the library clears its staged copies: the results may be secret keys)
+    pub fn hash_to_scalar(&self, curve: c_int, msgs: &[&[u8]], dst: &[u8]) -> Result<Vec<u8>, Error> {
+        let nb = Self::field_bytes(curve);
+        Self::arg(nb != 0)?;
+        let (rec, lens, stride) = Self::pack_messages(msgs);
+        let mut out = vec![0u8; nb * msgs.len()];
+        self.check(unsafe {
+            ecgpu_hash_to_scalar_batch(self.0, curve, rec.as_ptr(), stride, lens.as_ptr(), dst.as_ptr(), dst.len(), out.as_mut_ptr(), msgs.len(), ECGPU_MEM_HOST)
+        })?;
+        Ok(out)
+    }
+    /// VerifyingKey::verify_prehash for a batch of 32-byte digests: the BIP340 challenges are hashed on the device too
+    pub fn schnorr_verify_prehash(&self, pubkeys_x: &[u8], sig_rs: &[u8], prehashes: &[u8]) -> Result<Vec<u8>, Error> {
+        Self::arg(pubkeys_x.len() % 32 == 0 && sig_rs.len() == 2 * pubkeys_x.len() && prehashes.len() == pubkeys_x.len())?;
+        let mut ok = vec![0u8; pubkeys_x.len() / 32];
+        self.check(unsafe {
+            ecgpu_schnorr_verify_prehash_batch(self.0, ECGPU_K256, pubkeys_x.as_ptr(), sig_rs.as_ptr(), prehashes.as_ptr(), ok.as_mut_ptr(), ok.len(), ECGPU_MEM_HOST)
+        })?;
+        Ok(ok)
     }
     /// ToEncodedPoint::to_encoded_point(compress) in fixed-width records (identity: tag 0x00 and zero padding)
     pub fn sec1_encode(&self, curve: c_int, points: &[u8], point_format: c_int, compress: bool) -> Result<Vec<u8>, Error> {

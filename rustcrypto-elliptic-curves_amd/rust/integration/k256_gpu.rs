@@ -6,7 +6,7 @@
 //! (field.rs:118-120, field_5x52.rs:96-131), `Scalar::to_bytes` (scalar.rs:94-96); nothing here depends on the in-memory
 //! layout of the types (which is not ABI-stable, field_impl.rs:23-28).
 use alloc::vec::Vec;
-use ecgpu_sys::{Context, Error, Group, ECGPU_EXACT_REFERENCE, ECGPU_K256, ECGPU_PT_AFFINE, ECGPU_PT_PROJECTIVE, ECGPU_SC_INV};
+use ecgpu_sys::{Context, Error, Group, ECGPU_EXACT_REFERENCE, ECGPU_H2C_NU, ECGPU_H2C_RO, ECGPU_K256, ECGPU_PT_AFFINE, ECGPU_PT_PROJECTIVE, ECGPU_SC_INV};
 use elliptic_curve::{ff::PrimeField, subtle::{Choice, CtOption}};
 
 use crate::{AffinePoint, FieldBytes, ProjectivePoint, Scalar};
@@ -116,4 +116,30 @@ pub fn eq_batch(gpu: &Context, a: &[ProjectivePoint], b: &[ProjectivePoint]) -> 
     for q in a { put_projective(&mut pa, q); }
     for q in b { put_projective(&mut pb, q); }
     Ok(gpu.point_eq(ECGPU_K256, &pa, &pb)?.into_iter().map(|f| f != 0).collect())
+}
+
+/// `GroupDigest` for many messages under one DST (arithmetic/hash2curve.rs; the trait's methods take `&[&[u8]]` message
+/// parts and DST parts: concatenate them first).  SHA-256, expand_message_xmd, FromOkm, the two maps with their isogeny
+/// and the sum all run on the device.
+pub fn hash_from_bytes_batch(gpu: &Context, msgs: &[&[u8]], dst: &[u8]) -> Result<Vec<AffinePoint>, Error> {
+    let (xy, inf) = gpu.hash_to_curve(ECGPU_K256, msgs, dst, ECGPU_H2C_RO)?;
+    Ok(xy.chunks_exact(64).zip(inf.iter()).map(|(c, i)| get_affine(c, *i)).collect())
+}
+/// `GroupDigest::encode_from_bytes` (the nonuniform encoding: one map per message).
+pub fn encode_from_bytes_batch(gpu: &Context, msgs: &[&[u8]], dst: &[u8]) -> Result<Vec<AffinePoint>, Error> {
+    let (xy, inf) = gpu.hash_to_curve(ECGPU_K256, msgs, dst, ECGPU_H2C_NU)?;
+    Ok(xy.chunks_exact(64).zip(inf.iter()).map(|(c, i)| get_affine(c, *i)).collect())
+}
+/// `GroupDigest::hash_to_scalar`.
+pub fn hash_to_scalar_batch(gpu: &Context, msgs: &[&[u8]], dst: &[u8]) -> Result<Vec<Scalar>, Error> {
+    let out = gpu.hash_to_scalar(ECGPU_K256, msgs, dst)?;
+    // the library only returns canonical scalars: from_repr cannot fail on them
+    Ok(out.chunks_exact(32).map(|b| Scalar::from_repr(*FieldBytes::from_slice(b)).unwrap()).collect())
+}
+/// BIP340 `VerifyingKey::verify_prehash` (schnorr/verifying.rs:62-93) for many (key, digest, signature) triples: the tagged
+/// challenge hash runs on the device as well.
+pub fn schnorr_verify_prehash_batch(gpu: &Context, pubkeys_x: &[[u8; 32]], prehashes: &[[u8; 32]], sigs: &[[u8; 64]]) -> Result<Vec<bool>, Error> {
+    assert!(pubkeys_x.len() == prehashes.len() && prehashes.len() == sigs.len());
+    let ok = gpu.schnorr_verify_prehash(&pubkeys_x.concat(), &sigs.concat(), &prehashes.concat())?;
+    Ok(ok.into_iter().map(|f| f != 0).collect())
 }

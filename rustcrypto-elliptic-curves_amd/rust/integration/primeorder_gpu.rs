@@ -5,7 +5,7 @@
 //! leaves the Montgomery domain first: p256 field.rs:281-284, fiat_p384_from_montgomery); scalars as `to_repr` too
 //! (p384's `Scalar` is in Montgomery form internally, scalar.rs:335-339 - `to_repr` canonicalises it).
 use alloc::vec::Vec;
-use ecgpu_sys::{Context, Error, ECGPU_EXACT_REFERENCE, ECGPU_P256, ECGPU_P384, ECGPU_PT_AFFINE, ECGPU_PT_PROJECTIVE};
+use ecgpu_sys::{Context, Error, ECGPU_EXACT_REFERENCE, ECGPU_H2C_NU, ECGPU_H2C_RO, ECGPU_P256, ECGPU_P384, ECGPU_PT_AFFINE, ECGPU_PT_PROJECTIVE};
 use elliptic_curve::{ff::PrimeField, FieldBytes, Scalar};
 
 use crate::{AffinePoint, PrimeCurveParams, ProjectivePoint};
@@ -84,4 +84,23 @@ pub fn eq_batch<C: GpuCurve>(gpu: &Context, a: &[ProjectivePoint<C>], b: &[Proje
     for q in a { put_projective::<C>(&mut pa, q); }
     for q in b { put_projective::<C>(&mut pb, q); }
     Ok(gpu.point_eq(C::ECGPU_ID, &pa, &pb)?.into_iter().map(|f| f != 0).collect())
+}
+
+/// `GroupDigest` for many messages under one DST (p256 | p384 src/arithmetic/hash2curve.rs; the trait's methods take
+/// `&[&[u8]]` message parts and DST parts: concatenate them first).  SHA-2, expand_message_xmd, FromOkm, the maps and their
+/// sum all run on the device.
+pub fn hash_from_bytes_batch<C: GpuCurve>(gpu: &Context, msgs: &[&[u8]], dst: &[u8]) -> Result<Vec<AffinePoint<C>>, Error> {
+    let (xy, inf) = gpu.hash_to_curve(C::ECGPU_ID, msgs, dst, ECGPU_H2C_RO)?;
+    Ok(xy.chunks_exact(2 * nb::<C>()).zip(inf.iter()).map(|(c, i)| get_affine::<C>(c, *i)).collect())
+}
+/// `GroupDigest::encode_from_bytes` (the nonuniform encoding: one map per message).
+pub fn encode_from_bytes_batch<C: GpuCurve>(gpu: &Context, msgs: &[&[u8]], dst: &[u8]) -> Result<Vec<AffinePoint<C>>, Error> {
+    let (xy, inf) = gpu.hash_to_curve(C::ECGPU_ID, msgs, dst, ECGPU_H2C_NU)?;
+    Ok(xy.chunks_exact(2 * nb::<C>()).zip(inf.iter()).map(|(c, i)| get_affine::<C>(c, *i)).collect())
+}
+/// `GroupDigest::hash_to_scalar` (VOPRF DeriveKeyPair and friends: the results may be secret keys).
+pub fn hash_to_scalar_batch<C: GpuCurve>(gpu: &Context, msgs: &[&[u8]], dst: &[u8]) -> Result<Vec<Scalar<C>>, Error> {
+    let out = gpu.hash_to_scalar(C::ECGPU_ID, msgs, dst)?;
+    // the library only returns canonical scalars: from_repr cannot fail on them
+    Ok(out.chunks_exact(nb::<C>()).map(|b| Scalar::<C>::from_repr(FieldBytes::<C>::clone_from_slice(b)).unwrap()).collect())
 }
