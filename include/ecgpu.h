@@ -347,10 +347,34 @@ int ecgpu_ecdsa_verify_batch(ecgpu_ctx* ctx, int curve, const uint8_t* prehash, 
  * speed of the reference schedule on P-256 / P-384, whose mul_by_generator is the generic variable-base
  * multiplication); ECGPU_EXACT_REFERENCE in `flags` selects the reference's own mul_by_generator schedule (constant-time
  * as well), ECGPU_PUBLIC_SCALARS the digit-indexed throughput schedule.  The signatures are identical in all three.
- * Staged host copies of d and k are cleared before the call returns. */
+ * Staged host copies of d and k are cleared before the call returns.
+ * This is the hazmat primitive: the caller supplies one secret nonce per signature.  What SigningKey::sign_prehash does - derive
+ * the nonce from the key and the digest - is ecgpu_ecdsa_sign_prehash_batch below. */
 int ecgpu_ecdsa_sign_batch(ecgpu_ctx* ctx, int curve, const uint8_t* secret_d, const uint8_t* nonce_k,
                            const uint8_t* prehash, uint8_t* sig_rs, uint8_t* recovery_id, uint8_t* ok,
                            size_t n, int mem, unsigned flags);
+
+/* ---- deterministic signing: the nonce comes from the key and the digest (csrc/hmac_drbg.hpp, csrc/signing_kernels.hpp) ----
+ * RFC 6979 section 3.2 as SigningKey::sign_prehash of the external ecdsa crate uses it (the `rfc6979` and
+ * `prehash_signer_signing_with_*` tests of p256/src/ecdsa.rs:96-134, p384/src/ecdsa.rs:89-128): HMAC-DRBG on the curve's digest
+ * (SHA-256 for secp256k1 and P-256, SHA-384 for P-384) over the canonical key x and h1 = prehash mod n (Reduce::reduce_bytes of the
+ * field-sized prehash: bits2octets), one signature per lane.
+ *   prehash   n x field_bytes, after bits2field as for ecgpu_ecdsa_sign_batch
+ *   extra     NULL (PrehashSigner::sign_prehash: no additional data) or n x field_bytes of additional data
+ *             (RandomizedPrehashSigner::sign_prehash_with_rng passes field_bytes random bytes)
+ * out_k[i] = the nonce, 0 < k < n, or zeros where d is outside [1, n-1].  Keys, additional data and nonces are secrets: their staged
+ * copies are cleared before the call returns.  Constant time in all of them except for the candidate rejection the RFC prescribes
+ * (probability 2^-32 on P-256, 2^-128 on secp256k1, 2^-194 on P-384 per signature). */
+int ecgpu_rfc6979_nonce_batch(ecgpu_ctx* ctx, int curve, const uint8_t* secret_d, const uint8_t* prehash,
+                              const uint8_t* extra, uint8_t* out_k, size_t n, int mem);
+/* PrehashSigner::sign_prehash (extra == NULL) / RandomizedPrehashSigner::sign_prehash_with_rng (extra given) for a batch: the nonce
+ * kernel writes k into the context's intermediate workspace, ecgpu_ecdsa_sign_batch's pipeline runs on it (constant-time fixed
+ * base by default; ECGPU_EXACT_REFERENCE and ECGPU_ECDSA_LOW_S as there), and the nonces are cleared from the workspace whichever
+ * way the call ends.  ECGPU_PUBLIC_SCALARS is refused with ECGPU_ERR_ARG: a nonce derived from the key is never public.
+ * sig_rs, recovery_id (optional) and ok as for ecgpu_ecdsa_sign_batch; ok[i] = 0 and a zero signature for d outside [1, n-1]. */
+int ecgpu_ecdsa_sign_prehash_batch(ecgpu_ctx* ctx, int curve, const uint8_t* secret_d, const uint8_t* prehash,
+                                   const uint8_t* extra, uint8_t* sig_rs, uint8_t* recovery_id, uint8_t* ok,
+                                   size_t n, int mem, unsigned flags);
 
 /* Public-key recovery, VerifyingKey::recover_from_prehash (external ecdsa crate; exercised by k256/src/ecdsa.rs:259-336):
  * R = decompress(r, or r + n when recovery_id bit 1 is set; y parity = bit 0), Q = -(z r^-1) G + (s r^-1) R.
@@ -385,6 +409,17 @@ int ecgpu_schnorr_verify_batch(ecgpu_ctx* ctx, int curve, const uint8_t* pubkeys
  * only: other curves give ECGPU_ERR_UNSUPPORTED. */
 int ecgpu_schnorr_verify_prehash_batch(ecgpu_ctx* ctx, int curve, const uint8_t* pubkeys_x, const uint8_t* sig_rs,
                                        const uint8_t* prehash, uint8_t* ok, size_t n, int mem);
+
+/* SigningKey::sign_prehash_with_aux_rand (k256/src/schnorr/signing.rs:79-120) for a batch; secp256k1 only, other curves give
+ * ECGPU_ERR_UNSUPPORTED.  secret_keys, prehash, aux_rand: n x 32 bytes.  P = d G and R = k G run on the constant-time fixed-base
+ * kernel; d' = d or n - d by the parity of y(P), t = d' ^ H_aux(aux_rand), rand = H_nonce(t || x(P) || m), k = rand or n - rand by
+ * the parity of y(R), e = H_challenge(x(R) || x(P) || m) mod n, s = k + e d'.  sig_rs[i] = x(R) || s, pubkeys_x[i] (optional) = x(P),
+ * ok[i] = 1 - or zeros and ok[i] = 0 where the reference returns Err: d outside [1, n-1], rand outside [1, n-1] (NonZeroScalar::try_from
+ * refuses it; it is NOT reduced mod n as in BIP340's text), s = 0.  The public key is recomputed by every call.  Staged keys and
+ * aux_rand are cleared before the call returns, the nonces from the workspace too; d' and t never leave the registers. */
+int ecgpu_schnorr_sign_prehash_batch(ecgpu_ctx* ctx, int curve, const uint8_t* secret_keys, const uint8_t* prehash,
+                                     const uint8_t* aux_rand, uint8_t* sig_rs, uint8_t* pubkeys_x, uint8_t* ok,
+                                     size_t n, int mem);
 
 /* ---- hash to curve (RFC 9380 suites *_XMD:SHA-*_SSWU_RO_ / _NU_) ------------------------------------------------
  * MapToCurve::map_to_curve and the sum of GroupDigest::hash_from_bytes (k256|p256|p384/src/arithmetic/hash2curve.rs):

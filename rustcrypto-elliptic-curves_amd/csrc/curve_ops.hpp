@@ -7,6 +7,7 @@
 #include "ecdh_kernels.hpp"
 #include "sec1_kernels.hpp"
 #include "schnorr_kernels.hpp"
+#include "signing_kernels.hpp"
 #include "h2c_kernels.hpp"
 #include "h2c_hash.hpp"
 #include "straus.hpp"
@@ -487,6 +488,49 @@ struct CurveOps {
     HIPCHK(c, hipGetLastError());
     return 0;
   }
+  // Deterministic signing (signing_kernels.hpp).  The derived nonces pass through the intermediate workspace and are secrets of the
+  // key's rank: they are cleared on the stream whichever way the launcher is left (the fixed-base kernels keep nothing of a scalar).
+  struct NonceWipe {
+    ecgpu_ctx* c; void* p; size_t b;
+    ~NonceWipe() { (void)hipMemsetAsync(p, 0, b, c->stream); }
+  };
+  static int rfc6979_nonce(ecgpu_ctx* c, const u32* d, const u32* z, const u32* extra, u32* k, size_t n) {
+    const unsigned g = ecgpu_grid_for(c, n, 8);
+    if (extra) hipLaunchKernelGGL((sign::rfc6979_nonce_kernel<C, true>), dim3(g), dim3(256), 0, c->stream, d, z, extra, k, n);
+    else hipLaunchKernelGGL((sign::rfc6979_nonce_kernel<C, false>), dim3(g), dim3(256), 0, c->stream, d, z, extra, k, n);
+    HIPCHK(c, hipGetLastError());
+    return 0;
+  }
+  static int ecdsa_sign_prehash(ecgpu_ctx* c, const u32* d, const u32* z, const u32* extra, u32* sig, uint8_t* recid, uint8_t* ok, size_t n, unsigned flags) {
+    // the first two sub-buffers are ecdsa_sign's own layout: it carves them again at the same offsets, finds the workspace large enough
+    // (no reallocation, which would lose the nonces) and leaves the third alone
+    u32* k;
+    int rc = carve(c, [&](Carver& ws) { (void)ws.template take<u32>(n * 2 * C::NB); (void)ws.template take<uint8_t>(n); k = ws.template take<u32>(n * C::NB); });
+    if (rc) return rc;
+    NonceWipe wipe{c, k, n * C::NB};
+    if ((rc = rfc6979_nonce(c, d, z, extra, k, n))) return rc;
+    return ecdsa_sign(c, d, k, z, sig, recid, ok, n, flags);
+  }
+  // BIP340 (secp256k1 only): P = d G, the nonce kernel, R = k G, the finish kernel
+  static int schnorr_sign_prehash(ecgpu_ctx* c, const u32* d, const u32* m, const u32* aux, u32* sig, u32* pubkeys_x, uint8_t* ok, size_t n) {
+    if constexpr (C::ID != 0) {
+      return ecgpu_set_err(c, ECGPU_ERR_UNSUPPORTED, "ecgpu_schnorr_sign_prehash_batch: BIP340 is defined over secp256k1 only");
+    } else {
+      u32 *p_xy, *r_xy, *k;
+      int rc = carve(c, [&](Carver& ws) { p_xy = ws.template take<u32>(n * 2 * C::NB); r_xy = ws.template take<u32>(n * 2 * C::NB); k = ws.template take<u32>(n * C::NB); });
+      if (rc) return rc;
+      NonceWipe wipe{c, k, n * C::NB};
+      const unsigned g = ecgpu_grid_for(c, n, 8);
+      if ((rc = mul_gen_ct(c, d, p_xy, FMT_AFFINE, nullptr, n))) return rc;
+      hipLaunchKernelGGL((sign::schnorr_nonce_kernel<0>), dim3(g), dim3(256), 0, c->stream, d, (const u32*)p_xy, aux, m, k, n);
+      HIPCHK(c, hipGetLastError());
+      if ((rc = mul_gen_ct(c, k, r_xy, FMT_AFFINE, nullptr, n))) return rc;
+      hipLaunchKernelGGL((sign::schnorr_finish_kernel<0>), dim3(g), dim3(256), 0, c->stream, d, (const u32*)p_xy, (const u32*)k, (const u32*)r_xy, m, sig,
+                         pubkeys_x, ok, n);
+      HIPCHK(c, hipGetLastError());
+      return 0;
+    }
+  }
   // scalar field (scalar_ops.hpp): element-wise ops one lane per element, inversions SCALAR_INV_BATCH per lane
   static int scalar_op(ecgpu_ctx* c, int op, const u32* a, const u32* b, u32* o, uint8_t* ok, size_t n) {
     using O = OrderOf<C>;
@@ -540,7 +584,8 @@ struct CurveOps {
   static const ecgpu_curve_ops* table() {
     static const ecgpu_curve_ops t = {field_op, point_op, point_eq, normalize, lincomb, msm, validate_scalars, validate_points,
                                       decompress, synth_scalars, synth_points, to_bytes, from_bytes, sec1_encode, sec1_decode, ecdsa_verify, h2c_map, ecdsa_recover, schnorr_verify, ecdsa_sign, ecdh,
-                                      pass_units, scalar_op, scalar_reduce, h2c_hash_to_field, field_from_okm, schnorr_challenge};
+                                      pass_units, scalar_op, scalar_reduce, h2c_hash_to_field, field_from_okm, schnorr_challenge,
+                                      rfc6979_nonce, ecdsa_sign_prehash, schnorr_sign_prehash};
     return &t;
   }
 };

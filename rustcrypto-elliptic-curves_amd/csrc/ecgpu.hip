@@ -170,7 +170,7 @@ static const ecgpu_curve_ops* ops_for(int curve) {
 
 extern "C" {
 
-const char* ecgpu_version(void) { return "ecgpu 0.6 (gfx950)"; }
+const char* ecgpu_version(void) { return "ecgpu 0.7 (gfx950)"; }
 
 size_t ecgpu_field_bytes(int curve) {
   switch (curve) {
@@ -679,6 +679,49 @@ int ecgpu_ecdsa_sign_batch(ecgpu_ctx* c, int curve, const uint8_t* secret_d, con
   return run_batch(c, mem, n, args, ops->pass_units(c, 0, 1, fb_flags), [&](void** d, size_t cnt) {
     return ops->ecdsa_sign(c, (const uint32_t*)d[0], (const uint32_t*)d[1], (const uint32_t*)d[2], (uint32_t*)d[3], (uint8_t*)d[4], (uint8_t*)d[5], cnt,
                            flags);
+  });
+}
+
+// ---------------------------------------------------------------------------------------------
+// deterministic signing (signing_kernels.hpp): the nonce is derived on the device from the key and the digest.  Keys, additional
+// data and aux_rand are staged as secrets; a derived nonce leaves the device only through ecgpu_rfc6979_nonce_batch, as a secret too.
+// ---------------------------------------------------------------------------------------------
+int ecgpu_rfc6979_nonce_batch(ecgpu_ctx* c, int curve, const uint8_t* secret_d, const uint8_t* prehash, const uint8_t* extra, uint8_t* out_k, size_t n,
+                              int mem) {
+  if (!c || !secret_d || !prehash || !out_k) return ecgpu_set_err(c, ECGPU_ERR_ARG, "null argument");
+  if (n == 0) return ECGPU_OK;
+  ENTER(c, curve);
+  const CallArg args[] = {arg_in(secret_d, nb, ARG_SECRET), arg_in(prehash, nb), arg_in(extra, nb, ARG_SECRET | ARG_OPTIONAL), arg_out(out_k, nb, ARG_SECRET)};
+  return run_batch(c, mem, n, args, (size_t)1 << 22, [&](void** d, size_t cnt) {
+    return ops->rfc6979_nonce(c, (const uint32_t*)d[0], (const uint32_t*)d[1], (const uint32_t*)d[2], (uint32_t*)d[3], cnt);
+  });
+}
+int ecgpu_ecdsa_sign_prehash_batch(ecgpu_ctx* c, int curve, const uint8_t* secret_d, const uint8_t* prehash, const uint8_t* extra, uint8_t* sig_rs,
+                                   uint8_t* recovery_id, uint8_t* ok, size_t n, int mem, unsigned flags) {
+  if (!c || !secret_d || !prehash || !sig_rs || !ok) return ecgpu_set_err(c, ECGPU_ERR_ARG, "null argument");
+  if (flags & ECGPU_PUBLIC_SCALARS)
+    return ecgpu_set_err(c, ECGPU_ERR_ARG, "ecgpu_ecdsa_sign_prehash_batch: ECGPU_PUBLIC_SCALARS is refused (a nonce derived from the key is never public)");
+  if (n == 0) return ECGPU_OK;
+  ENTER(c, curve);
+  const CallArg args[] = {arg_in(secret_d, nb, ARG_SECRET), arg_in(prehash, nb), arg_in(extra, nb, ARG_SECRET | ARG_OPTIONAL),
+                          arg_out(sig_rs, 2 * nb), arg_out(recovery_id, 1, ARG_OPTIONAL), arg_out(ok, 1)};
+  const unsigned fb_flags = (flags & ECGPU_EXACT_REFERENCE) ? (unsigned)ECGPU_EXACT_REFERENCE : (unsigned)ECGPU_SECRET_SCALARS;
+  return run_batch(c, mem, n, args, ops->pass_units(c, 0, 1, fb_flags), [&](void** d, size_t cnt) {
+    return ops->ecdsa_sign_prehash(c, (const uint32_t*)d[0], (const uint32_t*)d[1], (const uint32_t*)d[2], (uint32_t*)d[3], (uint8_t*)d[4], (uint8_t*)d[5],
+                                   cnt, flags);
+  });
+}
+int ecgpu_schnorr_sign_prehash_batch(ecgpu_ctx* c, int curve, const uint8_t* secret_keys, const uint8_t* prehash, const uint8_t* aux_rand, uint8_t* sig_rs,
+                                     uint8_t* pubkeys_x, uint8_t* ok, size_t n, int mem) {
+  if (!c || !secret_keys || !prehash || !aux_rand || !sig_rs || !ok) return ecgpu_set_err(c, ECGPU_ERR_ARG, "null argument");
+  if (ecgpu_field_bytes(curve) && curve != ECGPU_K256)
+    return ecgpu_set_err(c, ECGPU_ERR_UNSUPPORTED, "ecgpu_schnorr_sign_prehash_batch: BIP340 is defined over secp256k1 only");
+  if (n == 0) return ECGPU_OK;
+  ENTER(c, curve);
+  const CallArg args[] = {arg_in(secret_keys, nb, ARG_SECRET), arg_in(prehash, 32), arg_in(aux_rand, 32, ARG_SECRET),
+                          arg_out(sig_rs, 2 * nb), arg_out(pubkeys_x, nb, ARG_OPTIONAL), arg_out(ok, 1)};
+  return run_batch(c, mem, n, args, ops->pass_units(c, 0, 1, ECGPU_SECRET_SCALARS), [&](void** d, size_t cnt) {
+    return ops->schnorr_sign_prehash(c, (const uint32_t*)d[0], (const uint32_t*)d[1], (const uint32_t*)d[2], (uint32_t*)d[3], (uint32_t*)d[4], (uint8_t*)d[5], cnt);
   });
 }
 

@@ -175,6 +175,14 @@ struct ecgpu_curve_ops {
                            uint32_t* u, size_t n);
   int (*field_from_okm)(ecgpu_ctx* c, const uint8_t* okm, uint32_t* out, size_t n);
   int (*schnorr_challenge)(ecgpu_ctx* c, const uint32_t* px, const uint32_t* sig, const uint32_t* prehash, uint32_t* e, size_t n);
+  // deterministic signing (signing_kernels.hpp).  rfc6979_nonce: k = n RFC 6979 nonces (extra may be NULL), 0 for a key out of range;
+  // ecdsa_sign_prehash: the nonces go through the workspace into ecdsa_sign and are cleared; schnorr_sign_prehash: BIP340
+  // sign_prehash_with_aux_rand (secp256k1 only; pubkeys_x may be NULL)
+  int (*rfc6979_nonce)(ecgpu_ctx* c, const uint32_t* d, const uint32_t* z, const uint32_t* extra, uint32_t* k, size_t n);
+  int (*ecdsa_sign_prehash)(ecgpu_ctx* c, const uint32_t* d, const uint32_t* z, const uint32_t* extra, uint32_t* sig, uint8_t* recid, uint8_t* ok,
+                            size_t n, unsigned flags);
+  int (*schnorr_sign_prehash)(ecgpu_ctx* c, const uint32_t* d, const uint32_t* m, const uint32_t* aux, uint32_t* sig, uint32_t* pubkeys_x, uint8_t* ok,
+                              size_t n);
 };
 // expand_message_xmd to raw bytes on `hash` (ecgpu_hash), curve-independent (h2c_hash.hip): out = n x tail.out_len bytes
 int ecgpuint_xmd(ecgpu_ctx* c, int hash, const uint8_t* msgs, size_t msg_stride, const uint32_t* msg_len, const ecgpu::h2c::XmdTail& tail, uint8_t* out, size_t n);

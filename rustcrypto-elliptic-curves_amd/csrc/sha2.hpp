@@ -232,6 +232,32 @@ ECGPU_HD u32 digest_byte(const typename H::W* d, u32 i) {
   return (u32)(w >> (8 * (WB - 1 - i % WB))) & 0xFFu;
 }
 
+// Word-wise placement for messages whose layout is known when the code is written (hmac_drbg.hpp: HMAC and the RFC 6979 DRBG).
+// m is a message as big-endian words, zeros where nothing has been placed yet, whole blocks long.  `pos` and `len` are byte
+// positions in it and are literals at every device call, so that after inlining and unrolling every index into m is a constant: a
+// secret word goes to one or two fixed slots by a fixed shift, and no load is addressed by a position as in `update`.
+template <class H>
+ECGPU_HD void place_word(typename H::W* m, u32 pos, typename H::W word) {
+  constexpr u32 WB = sizeof(typename H::W);
+  const u32 j = pos / WB, sh = 8 * (pos % WB);
+  m[j] |= word >> sh;
+  if (sh) m[j + 1] |= word << (8 * WB - sh);
+}
+template <class H>
+ECGPU_HD void place_byte(typename H::W* m, u32 pos, u32 byte) {
+  constexpr u32 WB = sizeof(typename H::W);
+  m[pos / WB] |= (typename H::W)byte << (8 * (WB - 1 - pos % WB));
+}
+// blocks that a message of len bytes fills once padded
+template <class H>
+ECGPU_HD constexpr u32 padded_blocks(u32 len) { return (len + 1 + H::LEN_BYTES + H::BLOCK_BYTES - 1) / H::BLOCK_BYTES; }
+// the 0x80 and the bit length of a message of len bytes that follows `prefix_blocks` blocks already compressed (lengths far below 2^29)
+template <class H>
+ECGPU_HD void pad_message(typename H::W* m, u32 len, u32 prefix_blocks) {
+  place_byte<H>(m, len, 0x80u);
+  m[16 * padded_blocks<H>(len) - 1] |= (typename H::W)((prefix_blocks * H::BLOCK_BYTES + len) << 3);
+}
+
 // one-shot
 template <class H>
 ECGPU_HD void hash(typename H::W* out, const uint8_t* p, u32 len) {

@@ -154,6 +154,9 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
     lib.ecgpu_hash_to_curve_batch.argtypes = [vp, i, u8p, sz, u8p, u8p, sz, i, u8p, u8p, sz, i]
     lib.ecgpu_hash_to_scalar_batch.argtypes = [vp, i, u8p, sz, u8p, u8p, sz, u8p, sz, i]
     lib.ecgpu_ecdsa_sign_batch.argtypes = [vp, i, u8p, u8p, u8p, u8p, u8p, u8p, sz, i, ctypes.c_uint]
+    lib.ecgpu_rfc6979_nonce_batch.argtypes = [vp, i, u8p, u8p, u8p, u8p, sz, i]
+    lib.ecgpu_ecdsa_sign_prehash_batch.argtypes = [vp, i, u8p, u8p, u8p, u8p, u8p, u8p, sz, i, ctypes.c_uint]
+    lib.ecgpu_schnorr_sign_prehash_batch.argtypes = [vp, i, u8p, u8p, u8p, u8p, u8p, u8p, sz, i]
     lib.ecgpu_synth_scalars.argtypes = [vp, i, ctypes.c_uint64, ctypes.c_uint64, u8p, sz]
     lib.ecgpu_synth_points.argtypes = [vp, i, ctypes.c_uint64, ctypes.c_uint64, u8p, sz]
     for name in ("ecgpu_create", "ecgpu_set_stream", "ecgpu_synchronize", "ecgpu_timer_start", "ecgpu_timer_stop",
@@ -168,7 +171,8 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
                  "ecgpu_ecdh_batch", "ecgpu_debug_workspace", "ecgpu_host_chunk_schedule", "ecgpu_group_create", "ecgpu_group_size",
                  "ecgpu_group_synchronize", "ecgpu_shard_range", "ecgpu_group_mul_batch", "ecgpu_group_lincomb_batch", "ecgpu_group_lincomb_sharded",
                  "ecgpu_group_msm", "ecgpu_group_msm_sharded", "ecgpu_schnorr_verify_prehash_batch", "ecgpu_expand_message_xmd_batch",
-                 "ecgpu_field_from_okm_batch", "ecgpu_hash_to_curve_batch", "ecgpu_hash_to_scalar_batch"):
+                 "ecgpu_field_from_okm_batch", "ecgpu_hash_to_curve_batch", "ecgpu_hash_to_scalar_batch", "ecgpu_rfc6979_nonce_batch",
+                 "ecgpu_ecdsa_sign_prehash_batch", "ecgpu_schnorr_sign_prehash_batch"):
         getattr(lib, name).restype = ctypes.c_int
     if path is None:
         _lib = lib
@@ -189,7 +193,7 @@ EXPORTED_SYMBOLS = (
     "ecgpu_group_synchronize", "ecgpu_shard_range", "ecgpu_group_mul_batch", "ecgpu_group_lincomb_batch", "ecgpu_group_lincomb_sharded",
     "ecgpu_group_msm", "ecgpu_group_msm_sharded",
     "ecgpu_schnorr_verify_prehash_batch", "ecgpu_expand_message_xmd_batch", "ecgpu_field_from_okm_batch", "ecgpu_hash_to_curve_batch",
-    "ecgpu_hash_to_scalar_batch",
+    "ecgpu_hash_to_scalar_batch", "ecgpu_rfc6979_nonce_batch", "ecgpu_ecdsa_sign_prehash_batch", "ecgpu_schnorr_sign_prehash_batch",
 )
 
 
@@ -693,6 +697,53 @@ class Curve:
         fl = self.default_ecdsa_flags() if flags is None else flags
         self.ctx.check(self.ctx.lib.ecgpu_ecdsa_sign_batch(self.ctx.handle, self.id, _ptr(d_secret)[0], _ptr(d_nonce)[0], _ptr(d_prehash)[0],
                                                            _ptr(d_sig_rs)[0], _ptr(d_recid)[0], _ptr(d_ok)[0], n, DEVICE, fl))
+
+    # --- deterministic signing: the nonce is derived on the device (RFC 6979 / BIP340) -------------------
+    def rfc6979_nonce(self, secret_d, prehash, extra=None) -> np.ndarray:
+        """the nonces SigningKey::sign_prehash derives (RFC 6979 on the curve's digest; `extra`: the additional data of the
+        randomized forms, field-sized) -> (n, NB); zeros for a key outside [1, n-1]"""
+        d, z = _as_host(secret_d, self.nb), _as_host(prehash, self.nb)
+        x = None if extra is None else _as_host(extra, self.nb)
+        if len(d) != len(z) or (x is not None and len(x) != len(d)):
+            raise ValueError("key, prehash and additional-data batches differ in length")
+        k = _host_out(len(d), self.nb)
+        self.ctx.check(self.ctx.lib.ecgpu_rfc6979_nonce_batch(self.ctx.handle, self.id, _ptr(d)[0], _ptr(z)[0], _ptr(x)[0], _ptr(k)[0], len(d), HOST))
+        return k
+
+    def rfc6979_nonce_device(self, d_secret, d_prehash, d_extra, d_out_k, n: int):
+        self.ctx.check(self.ctx.lib.ecgpu_rfc6979_nonce_batch(self.ctx.handle, self.id, _ptr(d_secret)[0], _ptr(d_prehash)[0], _ptr(d_extra)[0],
+                                                              _ptr(d_out_k)[0], n, DEVICE))
+
+    def ecdsa_sign_prehash(self, secret_d, prehash, extra=None, flags: Optional[int] = None):
+        """PrehashSigner::sign_prehash (extra=None) / RandomizedPrehashSigner (extra given) for a batch -> (sig_rs, recovery_id, ok)"""
+        d, z = _as_host(secret_d, self.nb), _as_host(prehash, self.nb)
+        x = None if extra is None else _as_host(extra, self.nb)
+        if len(d) != len(z) or (x is not None and len(x) != len(d)):
+            raise ValueError("key, prehash and additional-data batches differ in length")
+        sig, rec, ok = _host_out(len(d), 2 * self.nb), np.zeros(len(d), dtype=np.uint8), np.zeros(len(d), dtype=np.uint8)
+        fl = self.default_ecdsa_flags() if flags is None else flags
+        self.ctx.check(self.ctx.lib.ecgpu_ecdsa_sign_prehash_batch(self.ctx.handle, self.id, _ptr(d)[0], _ptr(z)[0], _ptr(x)[0], _ptr(sig)[0], _ptr(rec)[0],
+                                                                   _ptr(ok)[0], len(d), HOST, fl))
+        return sig, rec, ok
+
+    def ecdsa_sign_prehash_device(self, d_secret, d_prehash, d_extra, d_sig_rs, d_recid, d_ok, n: int, flags: Optional[int] = None):
+        fl = self.default_ecdsa_flags() if flags is None else flags
+        self.ctx.check(self.ctx.lib.ecgpu_ecdsa_sign_prehash_batch(self.ctx.handle, self.id, _ptr(d_secret)[0], _ptr(d_prehash)[0], _ptr(d_extra)[0],
+                                                                   _ptr(d_sig_rs)[0], _ptr(d_recid)[0], _ptr(d_ok)[0], n, DEVICE, fl))
+
+    def schnorr_sign_prehash(self, secret_keys, prehashes, aux_rands):
+        """BIP340 SigningKey::sign_prehash_with_aux_rand for a batch (secp256k1) -> (sig_rs, pubkeys_x, ok)"""
+        d, m, a = _as_host(secret_keys, self.nb), _as_host(prehashes, 32), _as_host(aux_rands, 32)
+        if not (len(d) == len(m) == len(a)):
+            raise ValueError("key, prehash and aux_rand batches differ in length")
+        sig, px, ok = _host_out(len(d), 2 * self.nb), _host_out(len(d), self.nb), np.zeros(len(d), dtype=np.uint8)
+        self.ctx.check(self.ctx.lib.ecgpu_schnorr_sign_prehash_batch(self.ctx.handle, self.id, _ptr(d)[0], _ptr(m)[0], _ptr(a)[0], _ptr(sig)[0], _ptr(px)[0],
+                                                                     _ptr(ok)[0], len(d), HOST))
+        return sig, px, ok
+
+    def schnorr_sign_prehash_device(self, d_secret, d_prehash, d_aux, d_sig_rs, d_pubkeys_x, d_ok, n: int):
+        self.ctx.check(self.ctx.lib.ecgpu_schnorr_sign_prehash_batch(self.ctx.handle, self.id, _ptr(d_secret)[0], _ptr(d_prehash)[0], _ptr(d_aux)[0],
+                                                                     _ptr(d_sig_rs)[0], _ptr(d_pubkeys_x)[0], _ptr(d_ok)[0], n, DEVICE))
 
     # --- synthetic inputs (device buffers) ---------------------------------------------------------
     def synth_scalars_device(self, d_out, n: int, seed: int, first_index: int = 0):

@@ -47,6 +47,14 @@ def verify_der_batch(curve: Curve, pubkeys_xy: Sequence[bytes], messages: Sequen
     return ok & decoded
 
 
+def sign_prehash(curve: Curve, secret_keys: Sequence[bytes], digests: Sequence[bytes], extra: Sequence[bytes] | None = None, flags=None):
+    """PrehashSigner::sign_prehash for a batch of digests of any admissible length: bits2field on the host, then
+    `Curve.ecdsa_sign_prehash` (ecgpu_ecdsa_sign_prehash_batch: RFC 6979 nonces and signatures on the device)
+    -> (sig_rs, recovery_id, ok).  `extra`: per-signature additional data of field size (RandomizedPrehashSigner)."""
+    z = b"".join(bits2field(curve.nb, bytes(h)) for h in digests)
+    return curve.ecdsa_sign_prehash(b"".join(secret_keys), z, None if extra is None else b"".join(extra), flags)
+
+
 ORDER = {
     K256: 0xFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFEBAAEDCE6AF48A03BBFD25E8CD0364141,
     P256: 0xFFFFFFFF00000000FFFFFFFFFFFFFFFFBCE6FAADA7179E84F3B9CAC2FC632551,

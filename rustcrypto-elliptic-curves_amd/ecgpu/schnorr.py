@@ -74,3 +74,17 @@ def sign_batch(curve: Curve, secret_keys: Sequence[bytes], prehashes: Sequence[b
             raise ValueError("zero s")
         sigs.append(r + s.to_bytes(32, "big"))
     return sigs, px
+
+
+def sign_batch_device(curve: Curve, secret_keys: Sequence[bytes], prehashes: Sequence[bytes], aux_rands: Sequence[bytes]):
+    """sign_batch with the tagged hashes and the arithmetic mod n on the device too (ecgpu_schnorr_sign_prehash_batch: one call,
+    no round trip) -> (signatures, public keys x-only).  Like the reference, and unlike sign_batch, a nonce hash outside
+    [1, n-1] is an error, not reduced (NonZeroScalar::try_from, signing.rs:105-108)."""
+    if curve.id != K256:
+        raise ValueError("BIP340 is defined over secp256k1")
+    if any(len(m) != 32 for m in prehashes):
+        raise ValueError("sign_prehash takes 32-byte digests")
+    sig, px, ok = curve.schnorr_sign_prehash(b"".join(secret_keys), b"".join(prehashes), b"".join(aux_rands))
+    if not ok.all():
+        raise ValueError("signing failed for element %d (secret key out of range, or a zero nonce or s)" % int(np.argmin(ok)))
+    return [bytes(r) for r in sig], [bytes(r) for r in px]

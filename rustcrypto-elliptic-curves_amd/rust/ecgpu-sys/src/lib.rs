@@ -128,6 +128,12 @@ extern "C" {
                                     mem: c_int, flags: c_uint) -> c_int;
     pub fn ecgpu_ecdsa_sign_batch(ctx: *mut ecgpu_ctx, curve: c_int, secret_d: *const u8, nonce_k: *const u8, prehash: *const u8, sig_rs: *mut u8,
                                   recovery_id: *mut u8, ok: *mut u8, n: usize, mem: c_int, flags: c_uint) -> c_int;
+    pub fn ecgpu_rfc6979_nonce_batch(ctx: *mut ecgpu_ctx, curve: c_int, secret_d: *const u8, prehash: *const u8, extra: *const u8, out_k: *mut u8, n: usize,
+                                     mem: c_int) -> c_int;
+    pub fn ecgpu_ecdsa_sign_prehash_batch(ctx: *mut ecgpu_ctx, curve: c_int, secret_d: *const u8, prehash: *const u8, extra: *const u8, sig_rs: *mut u8,
+                                          recovery_id: *mut u8, ok: *mut u8, n: usize, mem: c_int, flags: c_uint) -> c_int;
+    pub fn ecgpu_schnorr_sign_prehash_batch(ctx: *mut ecgpu_ctx, curve: c_int, secret_keys: *const u8, prehash: *const u8, aux_rand: *const u8, sig_rs: *mut u8,
+                                            pubkeys_x: *mut u8, ok: *mut u8, n: usize, mem: c_int) -> c_int;
     pub fn ecgpu_ecdsa_recover_batch(ctx: *mut ecgpu_ctx, curve: c_int, prehash: *const u8, sig_rs: *const u8, recovery_id: *const u8, pubkeys_xy: *mut u8,
                                      ok: *mut u8, n: usize, mem: c_int, flags: c_uint) -> c_int;
     pub fn ecgpu_ecdh_batch(ctx: *mut ecgpu_ctx, curve: c_int, secret_scalars: *const u8, pubkeys_xy: *const u8, shared_x: *mut u8, ok: *mut u8, n: usize,
@@ -377,6 +383,42 @@ impl Context {
                                    flags)
         })?;
         Ok((sig, rec, ok))
+    }
+    /// The RFC 6979 nonces `SigningKey::sign_prehash` derives, for a batch (`extra`: the additional data of the randomized forms);
+    /// zeros for a key outside [1, n-1].  The result is as secret as the keys.
+    pub fn rfc6979_nonce(&self, curve: c_int, secret_d: &[u8], prehash: &[u8], extra: Option<&[u8]>) -> Result<Vec<u8>, Error> {
+        let nb = Self::field_bytes(curve);
+        Self::arg(nb != 0 && secret_d.len() % nb == 0 && prehash.len() == secret_d.len() && extra.map_or(true, |e| e.len() == secret_d.len()))?;
+        let n = secret_d.len() / nb;
+        let mut k = vec![0u8; nb * n];
+        self.check(unsafe {
+            ecgpu_rfc6979_nonce_batch(self.0, curve, secret_d.as_ptr(), prehash.as_ptr(), extra.map_or(core::ptr::null(), |e| e.as_ptr()), k.as_mut_ptr(), n, ECGPU_MEM_HOST)
+        })?;
+        Ok(k)
+    }
+    /// `PrehashSigner::sign_prehash` (`extra = None`) / `RandomizedPrehashSigner::sign_prehash_with_rng` (`extra`: field-sized random
+    /// bytes per signature) for a batch -> (r || s, recovery ids, ok flags).  `ECGPU_PUBLIC_SCALARS` is refused.
+    pub fn ecdsa_sign_prehash(&self, curve: c_int, secret_d: &[u8], prehash: &[u8], extra: Option<&[u8]>, flags: c_uint) -> Result<(Vec<u8>, Vec<u8>, Vec<u8>), Error> {
+        let nb = Self::field_bytes(curve);
+        Self::arg(nb != 0 && secret_d.len() % nb == 0 && prehash.len() == secret_d.len() && extra.map_or(true, |e| e.len() == secret_d.len()))?;
+        let n = secret_d.len() / nb;
+        let (mut sig, mut rec, mut ok) = (vec![0u8; 2 * nb * n], vec![0u8; n], vec![0u8; n]);
+        self.check(unsafe {
+            ecgpu_ecdsa_sign_prehash_batch(self.0, curve, secret_d.as_ptr(), prehash.as_ptr(), extra.map_or(core::ptr::null(), |e| e.as_ptr()), sig.as_mut_ptr(),
+                                           rec.as_mut_ptr(), ok.as_mut_ptr(), n, ECGPU_MEM_HOST, flags)
+        })?;
+        Ok((sig, rec, ok))
+    }
+    /// BIP340 `SigningKey::sign_prehash_with_aux_rand` for a batch (secp256k1) -> (r || s, x-only public keys, ok flags)
+    pub fn schnorr_sign_prehash(&self, secret_keys: &[u8], prehashes: &[u8], aux_rands: &[u8]) -> Result<(Vec<u8>, Vec<u8>, Vec<u8>), Error> {
+        Self::arg(secret_keys.len() % 32 == 0 && prehashes.len() == secret_keys.len() && aux_rands.len() == secret_keys.len())?;
+        let n = secret_keys.len() / 32;
+        let (mut sig, mut px, mut ok) = (vec![0u8; 64 * n], vec![0u8; 32 * n], vec![0u8; n]);
+        self.check(unsafe {
+            ecgpu_schnorr_sign_prehash_batch(self.0, ECGPU_K256, secret_keys.as_ptr(), prehashes.as_ptr(), aux_rands.as_ptr(), sig.as_mut_ptr(), px.as_mut_ptr(),
+                                             ok.as_mut_ptr(), n, ECGPU_MEM_HOST)
+        })?;
+        Ok((sig, px, ok))
     }
     /// VerifyingKey::recover_from_prehash for a batch -> (x || y, ok flags)
     pub fn ecdsa_recover(&self, curve: c_int, prehash: &[u8], sig_rs: &[u8], recovery_id: &[u8], flags: c_uint) -> Result<(Vec<u8>, Vec<u8>), Error> {

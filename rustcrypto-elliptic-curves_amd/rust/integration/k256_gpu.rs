@@ -143,3 +143,28 @@ pub fn schnorr_verify_prehash_batch(gpu: &Context, pubkeys_x: &[[u8; 32]], preha
     let ok = gpu.schnorr_verify_prehash(&pubkeys_x.concat(), &sigs.concat(), &prehashes.concat())?;
     Ok(ok.into_iter().map(|f| f != 0).collect())
 }
+
+/// `PrehashSigner<Signature>::sign_prehash` of `ecdsa::SigningKey<Secp256k1>` for many (key, digest) pairs: RFC 6979 nonces
+/// (HMAC-DRBG on SHA-256), k G on the constant-time kernel, low-s normalisation as ecdsa.rs:182-196.  `digests`: after bits2field
+/// (32 bytes).  None where the reference returns Err.
+pub fn ecdsa_sign_prehash_batch(gpu: &Context, keys: &[Scalar], digests: &[[u8; 32]]) -> Result<Vec<Option<([u8; 64], u8)>>, Error> {
+    assert_eq!(keys.len(), digests.len());
+    let (sig, rec, ok) = gpu.ecdsa_sign_prehash(ECGPU_K256, &put_scalars(keys.iter()), &digests.concat(), None, ecgpu_sys::ECGPU_ECDSA_LOW_S)?;
+    Ok(sig.chunks_exact(64).zip(rec.iter().zip(ok.iter())).map(|(s, (r, k))| if *k != 0 { Some((s.try_into().unwrap(), *r)) } else { None }).collect())
+}
+/// `RandomizedPrehashSigner::sign_prehash_with_rng`: the same with 32 bytes of additional data per signature, drawn by the caller
+/// from its `CryptoRngCore` (the reference fills `ad` the same way before `try_sign_prehashed_rfc6979`).
+pub fn ecdsa_sign_prehash_randomized_batch(gpu: &Context, keys: &[Scalar], digests: &[[u8; 32]], added: &[[u8; 32]]) -> Result<Vec<Option<([u8; 64], u8)>>, Error> {
+    assert!(keys.len() == digests.len() && digests.len() == added.len());
+    let (sig, rec, ok) = gpu.ecdsa_sign_prehash(ECGPU_K256, &put_scalars(keys.iter()), &digests.concat(), Some(&added.concat()), ecgpu_sys::ECGPU_ECDSA_LOW_S)?;
+    Ok(sig.chunks_exact(64).zip(rec.iter().zip(ok.iter())).map(|(s, (r, k))| if *k != 0 { Some((s.try_into().unwrap(), *r)) } else { None }).collect())
+}
+/// BIP340 `schnorr::SigningKey::sign_prehash_with_aux_rand` (schnorr/signing.rs:79-120) for many (key, digest, aux_rand) triples:
+/// both generator multiplications, the three tagged hashes and the arithmetic mod n run on the device.  `secret_keys`: the
+/// `NonZeroScalar` bytes of the keys (the call recomputes each verifying key; no key pair is cached).  -> (signature, x-only key)
+pub fn schnorr_sign_prehash_batch(gpu: &Context, secret_keys: &[[u8; 32]], prehashes: &[[u8; 32]], aux_rands: &[[u8; 32]]) -> Result<Vec<Option<([u8; 64], [u8; 32])>>, Error> {
+    assert!(secret_keys.len() == prehashes.len() && prehashes.len() == aux_rands.len());
+    let (sig, px, ok) = gpu.schnorr_sign_prehash(&secret_keys.concat(), &prehashes.concat(), &aux_rands.concat())?;
+    Ok(sig.chunks_exact(64).zip(px.chunks_exact(32)).zip(ok.iter())
+        .map(|((s, p), k)| if *k != 0 { Some((s.try_into().unwrap(), p.try_into().unwrap())) } else { None }).collect())
+}

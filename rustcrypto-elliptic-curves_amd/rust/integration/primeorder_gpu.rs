@@ -104,3 +104,23 @@ pub fn hash_to_scalar_batch<C: GpuCurve>(gpu: &Context, msgs: &[&[u8]], dst: &[u
     // the library only returns canonical scalars: from_repr cannot fail on them
     Ok(out.chunks_exact(nb::<C>()).map(|b| Scalar::<C>::from_repr(FieldBytes::<C>::clone_from_slice(b)).unwrap()).collect())
 }
+
+/// `PrehashSigner<Signature<C>>::sign_prehash` of `ecdsa::SigningKey<C>` (p256/src/ecdsa.rs:120-134, p384/src/ecdsa.rs:114-128) for many
+/// (key, digest) pairs: RFC 6979 nonces on the curve's digest (HMAC-DRBG over SHA-256 / SHA-384), k G on the constant-time kernel,
+/// s = k^-1 (z + r d), all on the device.  `digests`: after bits2field (field-sized).  None where the reference returns Err.
+pub fn ecdsa_sign_prehash_batch<C: GpuCurve>(gpu: &Context, keys: &[Scalar<C>], digests: &[FieldBytes<C>]) -> Result<Vec<Option<(Vec<u8>, u8)>>, Error> {
+    ecdsa_sign_prehash_with(gpu, keys, digests, None)
+}
+/// `RandomizedPrehashSigner::sign_prehash_with_rng`: the same with field-sized additional data per signature, drawn by the caller
+/// from its `CryptoRngCore` (the reference fills `ad` the same way before `try_sign_prehashed_rfc6979`).
+pub fn ecdsa_sign_prehash_randomized_batch<C: GpuCurve>(gpu: &Context, keys: &[Scalar<C>], digests: &[FieldBytes<C>], added: &[FieldBytes<C>]) -> Result<Vec<Option<(Vec<u8>, u8)>>, Error> {
+    assert_eq!(added.len(), keys.len());
+    ecdsa_sign_prehash_with(gpu, keys, digests, Some(added))
+}
+fn ecdsa_sign_prehash_with<C: GpuCurve>(gpu: &Context, keys: &[Scalar<C>], digests: &[FieldBytes<C>], added: Option<&[FieldBytes<C>]>) -> Result<Vec<Option<(Vec<u8>, u8)>>, Error> {
+    assert_eq!(keys.len(), digests.len());
+    let flat = |v: &[FieldBytes<C>]| { let mut o = Vec::with_capacity(nb::<C>() * v.len()); for b in v { o.extend_from_slice(b.as_ref()); } o };
+    let ad = added.map(flat);
+    let (sig, rec, ok) = gpu.ecdsa_sign_prehash(C::ECGPU_ID, &put_scalars::<C>(keys.iter()), &flat(digests), ad.as_deref(), 0)?;
+    Ok(sig.chunks_exact(2 * nb::<C>()).zip(rec.iter().zip(ok.iter())).map(|(s, (r, k))| if *k != 0 { Some((s.to_vec(), *r)) } else { None }).collect())
+}
