@@ -272,28 +272,6 @@ struct CurveOps {
       return 0;
     }
   }
-  // Carves the intermediate workspace (c->ecdsa_ws) into sub-buffers of 256-byte-aligned sizes.  `layout` asks for them with
-  // take<T>(bytes), in order; it runs twice: once to add the sizes up, then, the workspace reserved, to receive the pointers.
-  struct Carver {
-    char* base;
-    size_t total = 0;
-    template <class T>
-    T* take(size_t bytes) {
-      T* p = base ? (T*)(base + total) : nullptr;
-      total += (bytes + 255) & ~(size_t)255;
-      return p;
-    }
-  };
-  template <class Layout>
-  static int carve(ecgpu_ctx* c, Layout layout) {
-    Carver sizes{nullptr};
-    layout(sizes);
-    int rc = ecgpu_reserve(c, c->ecdsa_ws, sizes.total);
-    if (rc) return rc;
-    Carver ws{(char*)c->ecdsa_ws.p};
-    layout(ws);
-    return 0;
-  }
   // 3 .. 1024 terms per combination, throughput schedule (straus.hpp): groups of up to 16 terms share the doublings of one window
   // loop over per-term affine tables; a second small kernel adds the groups' partial sums and writes the outputs
   static int lincomb_straus(ecgpu_ctx* c, const u32* sc, const u32* pts, int pt_fmt, size_t terms, u32* out, int out_fmt, uint8_t* out_inf, size_t n) {
@@ -307,7 +285,7 @@ struct CurveOps {
     int rc = ecgpu_reserve(c, c->tab_ws, (size_t)grid * 256 * sizeof(straus::LaneWs<C>));
     if (rc) return rc;
     u32* partial;
-    if ((rc = carve(c, [&](Carver& ws) { partial = ws.template take<u32>(items * 3 * C::NW * sizeof(u32)); }))) return rc;
+    if ((rc = ecgpu_carve(c, c->ecdsa_ws, [&](WsCarver& ws) { partial = ws.take<u32>(items * 3 * C::NW * sizeof(u32)); }))) return rc;
     unsigned long long* ctr = ecgpu_sched_counter(c);
     if (!ctr) return ECGPU_ERR_RUNTIME;
     hipLaunchKernelGGL((straus::lincomb_kernel<C, WAVES>), dim3(grid), dim3(256), 0, c->stream, sc, pts, pt_fmt, (int)terms, g, gpc, items,
@@ -364,7 +342,7 @@ struct CurveOps {
     if (pt_fmt == FMT_PROJECTIVE) {
       u32* t;
       uint8_t* ti;
-      int rc = carve(c, [&](Carver& ws) { t = ws.template take<u32>(n * 2 * C::NB); ti = ws.template take<uint8_t>(n); });
+      int rc = ecgpu_carve(c, c->ecdsa_ws, [&](WsCarver& ws) { t = ws.take<u32>(n * 2 * C::NB); ti = ws.take<uint8_t>(n); });
       if (rc) return rc;
       if ((rc = normalize(c, pts, t, ti, n))) return rc;
       xy = t; inf = ti;
@@ -389,17 +367,17 @@ struct CurveOps {
     uint8_t *a_inf, *b_inf;
   };
   static int verify_ws(ecgpu_ctx* c, size_t n, bool with_pt, VerifyWs& w) {
-    return carve(c, [&](Carver& ws) {
-      w.u1 = ws.template take<u32>(n * C::NB);
-      w.u2 = ws.template take<u32>(n * C::NB);
-      w.pt = with_pt ? ws.template take<u32>(n * 2 * C::NB) : nullptr;
-      w.a = ws.template take<u32>(n * 2 * C::NB);
-      w.b = ws.template take<u32>(n * 2 * C::NB);
-      w.a_inf = ws.template take<uint8_t>(n);
-      w.b_inf = ws.template take<uint8_t>(n);
+    return ecgpu_carve(c, c->ecdsa_ws, [&](WsCarver& ws) {
+      w.u1 = ws.take<u32>(n * C::NB);
+      w.u2 = ws.take<u32>(n * C::NB);
+      w.pt = with_pt ? ws.take<u32>(n * 2 * C::NB) : nullptr;
+      w.a = ws.take<u32>(n * 2 * C::NB);
+      w.b = ws.take<u32>(n * 2 * C::NB);
+      w.a_inf = ws.take<uint8_t>(n);
+      w.b_inf = ws.take<uint8_t>(n);
     });
   }
-  // a = u1 G, b = u2 Q (after the prep kernel's launch check)
+  // a = u1 G, b = u2 Q (after the prep kernel's launch check).  One term each: lincomb cannot reach lincomb_straus, which carves ecdsa_ws.
   static int verify_products(ecgpu_ctx* c, const VerifyWs& w, const u32* q, size_t n) {
     HIPCHK(c, hipGetLastError());
     int rc = lincomb(c, w.u1, nullptr, FMT_AFFINE, 1, w.a, FMT_AFFINE, w.a_inf, n, 0);
@@ -455,7 +433,7 @@ struct CurveOps {
   // one, the reference schedule otherwise), x of the product
   static int ecdh(ecgpu_ctx* c, const u32* d, const u32* q, u32* shared_x, uint8_t* ok, size_t n) {
     u32 *prod, *q_sane;
-    int rc = carve(c, [&](Carver& ws) { prod = ws.template take<u32>(n * 2 * C::NB); q_sane = ws.template take<u32>(n * 2 * C::NB); });
+    int rc = ecgpu_carve(c, c->ecdsa_ws, [&](WsCarver& ws) { prod = ws.take<u32>(n * 2 * C::NB); q_sane = ws.take<u32>(n * 2 * C::NB); });
     if (rc) return rc;
     // the products are secrets of the same rank as the shared values handed back: they do not stay in the workspace, whichever way
     // this function is left (the constant-time kernels clear what they park in the table workspace themselves)
@@ -470,12 +448,10 @@ struct CurveOps {
     HIPCHK(c, hipGetLastError());
     return 0;
   }
-  static int ecdsa_sign(ecgpu_ctx* c, const u32* d, const u32* k, const u32* z, u32* sig, uint8_t* recid, uint8_t* ok, size_t n,
-                        unsigned flags) {
-    u32* r_xy;
-    uint8_t* r_inf;
-    int rc = carve(c, [&](Carver& ws) { r_xy = ws.template take<u32>(n * 2 * C::NB); r_inf = ws.template take<uint8_t>(n); });
-    if (rc) return rc;
+  // R = k G into r_xy / r_inf (the caller's, out of its workspace layout), then the finish kernel
+  static int ecdsa_sign_body(ecgpu_ctx* c, const u32* d, const u32* k, const u32* z, u32* r_xy, uint8_t* r_inf, u32* sig, uint8_t* recid, uint8_t* ok,
+                             size_t n, unsigned flags) {
+    int rc;
     // The nonce is secret: k G runs on the constant-time fixed-base kernel (every table entry read, one masked addition per window,
     // no digit-dependent branch or address) - or, with ECGPU_EXACT_REFERENCE, on the reference's own mul_by_generator
     // schedule, which is constant-time as well - unless the caller declares the scalars public.
@@ -487,6 +463,14 @@ struct CurveOps {
                        (const u32*)r_xy, (const uint8_t*)r_inf, sig, recid, ok, n, flags);
     HIPCHK(c, hipGetLastError());
     return 0;
+  }
+  static int ecdsa_sign(ecgpu_ctx* c, const u32* d, const u32* k, const u32* z, u32* sig, uint8_t* recid, uint8_t* ok, size_t n,
+                        unsigned flags) {
+    u32* r_xy;
+    uint8_t* r_inf;
+    int rc = ecgpu_carve(c, c->ecdsa_ws, [&](WsCarver& ws) { r_xy = ws.take<u32>(n * 2 * C::NB); r_inf = ws.take<uint8_t>(n); });
+    if (rc) return rc;
+    return ecdsa_sign_body(c, d, k, z, r_xy, r_inf, sig, recid, ok, n, flags);
   }
   // Deterministic signing (signing_kernels.hpp).  The derived nonces pass through the intermediate workspace and are secrets of the
   // key's rank: they are cleared on the stream whichever way the launcher is left (the fixed-base kernels keep nothing of a scalar).
@@ -502,14 +486,17 @@ struct CurveOps {
     return 0;
   }
   static int ecdsa_sign_prehash(ecgpu_ctx* c, const u32* d, const u32* z, const u32* extra, u32* sig, uint8_t* recid, uint8_t* ok, size_t n, unsigned flags) {
-    // the first two sub-buffers are ecdsa_sign's own layout: it carves them again at the same offsets, finds the workspace large enough
-    // (no reallocation, which would lose the nonces) and leaves the third alone
-    u32* k;
-    int rc = carve(c, [&](Carver& ws) { (void)ws.template take<u32>(n * 2 * C::NB); (void)ws.template take<uint8_t>(n); k = ws.template take<u32>(n * C::NB); });
+    u32 *r_xy, *k;
+    uint8_t* r_inf;
+    int rc = ecgpu_carve(c, c->ecdsa_ws, [&](WsCarver& ws) {
+      r_xy = ws.take<u32>(n * 2 * C::NB);
+      r_inf = ws.take<uint8_t>(n);
+      k = ws.take<u32>(n * C::NB);
+    });
     if (rc) return rc;
     NonceWipe wipe{c, k, n * C::NB};
     if ((rc = rfc6979_nonce(c, d, z, extra, k, n))) return rc;
-    return ecdsa_sign(c, d, k, z, sig, recid, ok, n, flags);
+    return ecdsa_sign_body(c, d, k, z, r_xy, r_inf, sig, recid, ok, n, flags);
   }
   // BIP340 (secp256k1 only): P = d G, the nonce kernel, R = k G, the finish kernel
   static int schnorr_sign_prehash(ecgpu_ctx* c, const u32* d, const u32* m, const u32* aux, u32* sig, u32* pubkeys_x, uint8_t* ok, size_t n) {
@@ -517,7 +504,7 @@ struct CurveOps {
       return ecgpu_set_err(c, ECGPU_ERR_UNSUPPORTED, "ecgpu_schnorr_sign_prehash_batch: BIP340 is defined over secp256k1 only");
     } else {
       u32 *p_xy, *r_xy, *k;
-      int rc = carve(c, [&](Carver& ws) { p_xy = ws.template take<u32>(n * 2 * C::NB); r_xy = ws.template take<u32>(n * 2 * C::NB); k = ws.template take<u32>(n * C::NB); });
+      int rc = ecgpu_carve(c, c->ecdsa_ws, [&](WsCarver& ws) { p_xy = ws.take<u32>(n * 2 * C::NB); r_xy = ws.take<u32>(n * 2 * C::NB); k = ws.take<u32>(n * C::NB); });
       if (rc) return rc;
       NonceWipe wipe{c, k, n * C::NB};
       const unsigned g = ecgpu_grid_for(c, n, 8);

@@ -795,9 +795,9 @@ int ecgpu_hash_to_curve_batch(ecgpu_ctx* c, int curve, const uint8_t* msgs, size
                           arg_out(out_inf, 1, ARG_OPTIONAL)};
   return run_batch(c, mem, n, args, (size_t)1 << 22, [&](void** d, size_t cnt) {
     // the field elements go through the pipeline workspace (ecgpu_debug_workspace 1) in the layout the map kernel reads
-    int r = ecgpu_reserve(c, c->ecdsa_ws, cnt * count * nb);
+    uint32_t* u;
+    int r = ecgpu_carve(c, c->ecdsa_ws, [&](WsCarver& ws) { u = ws.take<uint32_t>(cnt * count * nb); });
     if (r) return r;
-    uint32_t* u = (uint32_t*)c->ecdsa_ws.p;
     if ((r = ops->h2c_hash_to_field(c, (const uint8_t*)d[0], msg_stride, (const uint32_t*)d[1], tail, count, u, cnt))) return r;
     return ops->h2c_map(c, u, count, (uint32_t*)d[2], (uint8_t*)d[3], cnt);
   });
@@ -815,9 +815,9 @@ int ecgpu_hash_to_scalar_batch(ecgpu_ctx* c, int curve, const uint8_t* msgs, siz
   ENTER(c, curve);
   const CallArg args[] = {arg_in(msg_stride ? msgs : nullptr, msg_stride, ARG_SECRET | ARG_OPTIONAL), arg_in(msg_len, 4, ARG_OPTIONAL), arg_out(out, nb, ARG_SECRET)};
   return run_batch(c, mem, n, args, (size_t)1 << 22, [&](void** d, size_t cnt) {
-    int r = ecgpu_reserve(c, c->ecdsa_ws, cnt * L);
+    uint8_t* okm;
+    int r = ecgpu_carve(c, c->ecdsa_ws, [&](WsCarver& ws) { okm = ws.take<uint8_t>(cnt * L); });
     if (r) return r;
-    uint8_t* okm = (uint8_t*)c->ecdsa_ws.p;
     struct OkmWipe {
       ecgpu_ctx* c; void* p; size_t b;
       ~OkmWipe() { (void)hipMemsetAsync(p, 0, b, c->stream); }
@@ -835,9 +835,9 @@ int ecgpu_schnorr_verify_prehash_batch(ecgpu_ctx* c, int curve, const uint8_t* p
   ENTER(c, curve);
   const CallArg args[] = {arg_in(pubkeys_x, nb), arg_in(sig_rs, 2 * nb), arg_in(prehash, 32), arg_out(ok, 1)};
   return run_batch(c, mem, n, args, ops->pass_units(c, 1, 1, 0), [&](void** d, size_t cnt) {
-    int r = ecgpu_reserve(c, c->hash_ws, cnt * 32);
+    uint32_t* e;
+    int r = ecgpu_carve(c, c->hash_ws, [&](WsCarver& ws) { e = ws.take<uint32_t>(cnt * 32); });
     if (r) return r;
-    uint32_t* e = (uint32_t*)c->hash_ws.p;
     if ((r = ops->schnorr_challenge(c, (const uint32_t*)d[0], (const uint32_t*)d[1], (const uint32_t*)d[2], e, cnt))) return r;
     return ops->schnorr_verify(c, (const uint32_t*)d[0], (const uint32_t*)d[1], e, (uint8_t*)d[3], cnt);
   });

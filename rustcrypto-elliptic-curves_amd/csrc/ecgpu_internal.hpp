@@ -9,6 +9,7 @@
 #include <mutex>
 
 #include "../../include/ecgpu.h"
+#include "ws_carver.hpp"
 #include "xmd_tail.hpp"
 
 // A grow-only device buffer (ecgpu_reserve below): scratch whose contents do not survive growing.
@@ -57,17 +58,20 @@ struct ecgpu_ctx {
   void* table[ECGPU_TAB_COUNT_][3] = {};             // [kind][curve]
   size_t fb_bytes[3] = {0, 0, 0};                      // device memory held by the generator tables of a curve
   int fb_widest[3] = {0, 0, 0};
-  // per-lane table workspace of the k256 variable-base kernel (grow-only)
+  // Workspaces (grow-only; DESIGN section 1, Workspaces).  The rule: the OUTERMOST launcher of a call carves a buffer, once
+  // (ecgpu_carve below); whatever it calls receives pointers and never carves that buffer again - growing loses the contents.
+  // per-lane tables of the variable-base, Straus and reference kernels: one buffer used whole, reserved by the launcher of that kernel
   DevBuf tab_ws;
-  // MSM workspace (grow-only)
+  // MSM workspace: carved by msm_run / msm_buckets (msm_kernels.hpp)
   DevBuf msm_ws;
   // work counters of the dynamically scheduled kernels (sched.hpp): a small ring, one 8-byte counter per launch, zeroed on the stream before it
   unsigned long long* sched_ctr = nullptr;
   unsigned sched_next = 0;
-  // intermediate scalars / points of the ECDSA pipelines (grow-only)
+  // intermediates of the pipelines: carved by the curve's entry launcher (curve_ops.hpp), or by the API layer (ecgpu.hip) where
+  // the launchers it strings together carve nothing
   DevBuf ecdsa_ws;
-  // BIP340 challenges of ecgpu_schnorr_verify_prehash_batch (grow-only): they live through the verification pipeline, which lays
-  // out ecdsa_ws for itself
+  // BIP340 challenges of ecgpu_schnorr_verify_prehash_batch, carved by the API layer: they live through schnorr_verify, which
+  // carves ecdsa_ws
   DevBuf hash_ws;
 };
 
@@ -99,6 +103,18 @@ static inline int ecgpu_reserve(ecgpu_ctx* c, DevBuf& b, size_t need) {
   b.cap = 0;
   HIPCHK(c, hipMalloc(&b.p, need));
   b.cap = need;
+  return 0;
+}
+// Carves `b` into the sub-buffers `layout` asks for (ws_carver.hpp): runs it once to add the sizes up, reserves, runs it again
+// to hand out the pointers.
+template <class Layout>
+static inline int ecgpu_carve(ecgpu_ctx* c, DevBuf& b, Layout&& layout) {
+  WsCarver sizes{nullptr};
+  layout(sizes);
+  int rc = ecgpu_reserve(c, b, sizes.total);
+  if (rc) return rc;
+  WsCarver ws{(char*)b.p};
+  layout(ws);
   return 0;
 }
 

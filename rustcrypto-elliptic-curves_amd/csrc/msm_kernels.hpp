@@ -1023,139 +1023,200 @@ __global__ void __launch_bounds__(256) to_affine_kernel(const u32* xyz, u32* xy,
 #ifndef MSM_ROUNDS
 #define MSM_ROUNDS 6                 // bucket-sum runs per resident lane (ECGPU_MSM_ROUNDS)
 #endif
-static inline size_t msm_align(size_t x) { return (x + 255) & ~(size_t)255; }
+// the four counters of a slab, zeroed before its sort: the kernels take the address of theirs (the heavy-bucket kernels read the
+// pair `heavy`, `heavy_chunks` through &heavy)
+struct SlabCounters {
+  u32 pieces;            // buckets left in pieces by the bucket sums (bucket_sum_kernel -> span_combine_kernel)
+  u32 big_bins;          // sort bins above BIG_BIN_TILES tiles (fine_sort_kernel -> big_*_kernel)
+  u32 heavy;             // buckets over more than SPAN_MAX runs (span_combine_kernel -> heavy_*_kernel)
+  u32 heavy_chunks;      // chunks those buckets are cut into
+};
+static_assert(sizeof(SlabCounters) == 16 && offsetof(SlabCounters, heavy_chunks) == offsetof(SlabCounters, heavy) + 4, "the heavy-bucket kernels index the pair");
 
-// the bucket method with CB-bit windows
+// Plan and workspace of the bucket method with CB-bit windows: the counts that size the buffers, and the buffers, each declared
+// once in layout().
 template <class C, int CB>
-static int msm_buckets(ecgpu_ctx* c, const u32* sc, const u32* pts, int pt_fmt, size_t n, u32* out, int out_fmt) {
+struct BucketWs {
   using G = Geo<CB>;
   using K = Cfg<C, CB>;
   using J = Jac<C>;
   using X = Xyzz<C>;
   using Mag = typename G::Mag;
-  constexpr int NW = C::NW, NHALF = K::NHALF, NWIN = K::NWIN, NDIG = K::NDIG;
-  constexpr int NCB = NWIN * G::NCOARSE;
-  constexpr int CARRY_WIN = K::HAS_CARRY ? NWIN - 1 : -1;
+  static constexpr int NW = C::NW, NHALF = K::NHALF, NWIN = K::NWIN, NDIG = K::NDIG;
+  static constexpr int NCB = NWIN * G::NCOARSE;
+  static constexpr int CARRY_WIN = K::HAS_CARRY ? NWIN - 1 : -1;
+  static constexpr size_t nb = (size_t)NWIN * G::NBUCKET;
+  static constexpr size_t n0 = nb / G::M;              // nodes of the level that reads the buckets
   static_assert((size_t)NDIG * G::SLAB_TERMS < ((size_t)1 << 32), "32-bit offsets within a slab");
-  auto al = msm_align;
-  const size_t nb = (size_t)NWIN * G::NBUCKET;
-  // Large sums run in slabs of at most SLAB_TERMS terms (a sorted entry keeps the term index in INDEX_BITS bits); every
-  // slab goes through the whole pipeline down to its NWIN window sums, which are added up before the final Horner pass.
-  // ECGPU_OPT_MSM_SLAB_TERMS overrides the slab size (tests exercise the slab loop on small inputs).
-  size_t slab = c->opt[ECGPU_OPT_MSM_SLAB_TERMS] ? (size_t)c->opt[ECGPU_OPT_MSM_SLAB_TERMS] : G::SLAB_TERMS;
-  if (slab < 1024 || slab > G::SLAB_TERMS) slab = G::SLAB_TERMS;
-  const size_t m = n < slab ? n : slab;                // terms of the largest slab: sizes the workspace
-  // bucket-sum runs: `rounds` per lane the chip holds at that kernel's occupancy (4 workgroups of 256 per CU)
-  const int rounds = (c->opt[ECGPU_OPT_MSM_ROUNDS] >= 1 && c->opt[ECGPU_OPT_MSM_ROUNDS] <= 64) ? (int)c->opt[ECGPU_OPT_MSM_ROUNDS] : MSM_ROUNDS;
-  const u32 ntask = (u32)rounds * (u32)c->num_cus * 256u * MSM_BS_WAVES;
-  const size_t sz_aff = (pt_fmt == FMT_PROJECTIVE) ? al(m * 8 * NW) : 0, sz_prep = al((size_t)NHALF * m * 8 * NW);
-  const size_t sz_off = al((nb + 1) * 4), sz_coff = al((size_t)(NCB + 1) * 4), sz_tot = al((size_t)NCB * 4), sz_sorted = al((size_t)NDIG * m * 4 + 32);
-  // level A of the sort: one 1024-thread workgroup per CU, the chunks of a window side by side
-  const int nch = (c->num_cus - 1) / NWIN > 0 ? (c->num_cus - 1) / NWIN : 1;
-  const size_t sz_part = al((size_t)NWIN * nch * G::NCOARSE * 4);
-  const size_t ms = (m + 3) & ~(size_t)3;              // row stride of the digit arrays: four terms per load
-  const size_t sz_mag = al((size_t)NDIG * ms * sizeof(Mag)), sz_sgn = al(ms * 4);
-  const size_t sz_bx = al(nb * sizeof(X)), sz_piece = al((size_t)ntask * sizeof(X)), sz_span = al((size_t)ntask * 4 + 8);
-  const size_t n0 = nb / G::M;                         // nodes of the level that reads the buckets
-  const size_t sz_l0 = al(n0 * sizeof(J)), sz_l1 = al(n0 / G::M * sizeof(J)), sz_grp = al(n0 / GROUP_NODES * 3 * sizeof(J)), sz_win = al(NWIN * sizeof(J));
+
+  bool projective;       // the input points are X:Y:Z and are normalised into `aff` first
+  size_t slab;           // terms per pass of the pipeline
+  size_t m, ms;          // terms of the largest slab; row stride of the digit arrays (four terms per load)
+  u32 ntask;             // bucket-sum runs
+  int nch;               // chunks of a window in level A of the sort
+  size_t hmax, cmax;     // most heavy buckets and chunks a slab can have
+  size_t maxbig;         // most big sort bins a slab can have
+
+  u32 *aff, *prep, *sgn, *offsets, *coarse_off, *tot, *part, *mid, *sorted, *span_list, *big_cnt, *big_list, *big_cur;
+  Mag* mag;
+  X *bucketsX, *head, *tail;
+  J *ta, *wa, *tb, *wb, *grp, *win, *win_slab, *partial;
+  SlabCounters* ctr;
+  HeavyBucket* heavy;
+  HeavyChunk* chunks;
+
+  BucketWs(const ecgpu_ctx* c, int pt_fmt, size_t n) : projective(pt_fmt == FMT_PROJECTIVE) {
+    // Large sums run in slabs of at most SLAB_TERMS terms (a sorted entry keeps the term index in INDEX_BITS bits); every
+    // slab goes through the whole pipeline down to its NWIN window sums, which are added up before the final Horner pass.
+    // ECGPU_OPT_MSM_SLAB_TERMS overrides the slab size (tests exercise the slab loop on small inputs).
+    slab = c->opt[ECGPU_OPT_MSM_SLAB_TERMS] ? (size_t)c->opt[ECGPU_OPT_MSM_SLAB_TERMS] : G::SLAB_TERMS;
+    if (slab < 1024 || slab > G::SLAB_TERMS) slab = G::SLAB_TERMS;
+    m = n < slab ? n : slab;
+    ms = (m + 3) & ~(size_t)3;
+    // bucket-sum runs: `rounds` per lane the chip holds at that kernel's occupancy (4 workgroups of 256 per CU)
+    const int rounds = (c->opt[ECGPU_OPT_MSM_ROUNDS] >= 1 && c->opt[ECGPU_OPT_MSM_ROUNDS] <= 64) ? (int)c->opt[ECGPU_OPT_MSM_ROUNDS] : MSM_ROUNDS;
+    ntask = (u32)rounds * (u32)c->num_cus * 256u * MSM_BS_WAVES;
+    // level A of the sort: one 1024-thread workgroup per CU, the chunks of a window side by side
+    nch = (c->num_cus - 1) / NWIN > 0 ? (c->num_cus - 1) / NWIN : 1;
+    // a run leaves at most two pieces (head and tail), so there are at most 2 ntask pieces: at most 2 ntask / SPAN_MAX buckets
+    // over more than SPAN_MAX runs, cut into at most 2 ntask / HEAVY_CHUNK + one chunk each
+    hmax = 2 * (size_t)ntask / SPAN_MAX + 1;
+    cmax = 2 * (size_t)ntask / HEAVY_CHUNK + hmax + 1;
+    // sort bins above BIG_BIN_TILES tiles: at most (entries of a slab) / (entries of such a bin) of them
+    maxbig = (size_t)NDIG * m / (BIG_BIN_TILES * FineTile<CB>::TILE) + 1;
+  }
+  size_t big_cnt_bytes() const { return maxbig * G::NFINE * 4; }
+  void layout(WsCarver& ws) {
+    aff = ws.take<u32>(projective ? m * 8 * NW : 0);
+    prep = ws.take<u32>((size_t)NHALF * m * 8 * NW);
+    mag = ws.take<Mag>((size_t)NDIG * ms * sizeof(Mag));
+    sgn = ws.take<u32>(ms * 4);
+    offsets = ws.take<u32>((nb + 1) * 4);
+    coarse_off = ws.take<u32>((size_t)(NCB + 1) * 4);
+    tot = ws.take<u32>((size_t)NCB * 4);
+    part = ws.take<u32>((size_t)NWIN * nch * G::NCOARSE * 4);
+    const size_t entries_bytes = (size_t)NDIG * m * 4 + 32;
+    mid = ws.take<u32>(entries_bytes);
+    sorted = ws.take<u32>(entries_bytes);
+    bucketsX = ws.take<X>(nb * sizeof(X));
+    const size_t pieces_bytes = (size_t)ntask * sizeof(X);
+    head = ws.take<X>(pieces_bytes);
+    tail = ws.take<X>(pieces_bytes);
+    span_list = ws.take<u32>((size_t)ntask * 4 + 8);
+    const size_t l0_bytes = n0 * sizeof(J), l1_bytes = n0 / G::M * sizeof(J), win_bytes = NWIN * sizeof(J);
+    ta = ws.take<J>(l0_bytes);
+    wa = ws.take<J>(l0_bytes);
+    tb = ws.take<J>(l1_bytes);
+    wb = ws.take<J>(l1_bytes);
+    grp = ws.take<J>(n0 / GROUP_NODES * 3 * sizeof(J));
+    win = ws.take<J>(win_bytes);
+    win_slab = ws.take<J>(win_bytes);
+    ctr = ws.take<SlabCounters>(sizeof(SlabCounters));
+    heavy = ws.take<HeavyBucket>(hmax * sizeof(HeavyBucket));
+    chunks = ws.take<HeavyChunk>(cmax * sizeof(HeavyChunk));
+    partial = ws.take<J>(cmax * sizeof(J));
+    big_cnt = ws.take<u32>(big_cnt_bytes());           // zeroed per slab; big_list is filled through the big_bins counter, big_cur by big_scan_kernel
+    big_list = ws.take<u32>(maxbig * 4);
+    big_cur = ws.take<u32>(big_cnt_bytes());
+  }
+};
+
+// One slab through the pipeline, in three stages on c->stream.  Digits and prepared points of `cnt` terms, then the two-level sort
+// of the digits into `sorted` with the bucket `offsets`.
+template <class C, int CB>
+static int msm_sort_slab(ecgpu_ctx* c, const BucketWs<C, CB>& w, const u32* ssc, const u32* xy, size_t cnt) {
+  using W = BucketWs<C, CB>;
+  using G = typename W::G;
+  using Mag = typename W::Mag;
+  constexpr int NWIN = W::NWIN, NHALF = W::NHALF, NCB = W::NCB, CARRY_WIN = W::CARRY_WIN;
+  const unsigned cb_grid = (unsigned)((NCB + 255) / 256);
+  u32* big_bins = &w.ctr->big_bins;
+  if (w.projective) {
+    hipLaunchKernelGGL((to_affine_kernel<C>), dim3(ecgpu_grid_for(c, cnt, 8)), dim3(256), 0, c->stream, xy, w.aff, cnt);
+    xy = w.aff;
+  }
+  hipLaunchKernelGGL((digits_kernel<C, CB>), dim3(ecgpu_grid_for(c, cnt, 8)), dim3(256), 0, c->stream, ssc, cnt, w.ms, w.mag, w.sgn);
+  hipLaunchKernelGGL((prepare_points_kernel<C>), dim3(ecgpu_grid_for(c, cnt, 8)), dim3(256), 0, c->stream, xy, w.prep, cnt);
+  hipLaunchKernelGGL((coarse_hist_kernel<CB>), dim3((unsigned)(NWIN * w.nch)), dim3(1024), 0, c->stream, (const Mag*)w.mag, cnt, w.ms, NHALF, w.nch, w.part);
+  hipLaunchKernelGGL(coarse_totals_kernel, dim3(cb_grid), dim3(256), 0, c->stream, (const u32*)w.part, NCB, G::NCOARSE, w.nch, w.tot);
+  hipLaunchKernelGGL(coarse_scan_kernel, dim3(1), dim3(1024), 0, c->stream, (const u32*)w.tot, NCB, w.coarse_off, w.offsets + W::nb);
+  hipLaunchKernelGGL(coarse_cursors_kernel, dim3(cb_grid), dim3(256), 0, c->stream, w.part, NCB, G::NCOARSE, w.nch, (const u32*)w.coarse_off);
+  hipLaunchKernelGGL((coarse_scatter_kernel<CB>), dim3((unsigned)(NWIN * w.nch)), dim3(1024), sizeof(typename CoarseTile<CB>::Lds), c->stream, (const Mag*)w.mag, (const u32*)w.sgn,
+                     cnt, w.ms, NHALF, CARRY_WIN, w.nch, (const u32*)w.part, w.mid, w.sorted);
+  HIPCHK(c, hipMemsetAsync(w.ctr, 0, sizeof(SlabCounters), c->stream));
+  HIPCHK(c, hipMemsetAsync(w.big_cnt, 0, w.big_cnt_bytes(), c->stream));
+  hipLaunchKernelGGL((fine_sort_kernel<CB>), dim3((unsigned)NCB), dim3(256), 0, c->stream, (const u32*)w.mid, (const u32*)w.coarse_off, CARRY_WIN, w.offsets, w.sorted,
+                     big_bins, w.big_list);
+  hipLaunchKernelGGL((big_count_kernel<CB>), dim3((unsigned)c->num_cus * 4), dim3(256), 0, c->stream, (const u32*)w.mid, (const u32*)w.coarse_off, (const u32*)big_bins,
+                     (const u32*)w.big_list, w.big_cnt);
+  hipLaunchKernelGGL((big_scan_kernel<CB>), dim3(64), dim3(256), 0, c->stream, (const u32*)w.coarse_off, (const u32*)big_bins, (const u32*)w.big_list, (const u32*)w.big_cnt,
+                     w.big_cur, w.offsets);
+  hipLaunchKernelGGL((big_place_kernel<CB>), dim3((unsigned)c->num_cus * 4), dim3(256), 0, c->stream, (const u32*)w.mid, (const u32*)w.coarse_off, (const u32*)big_bins,
+                     (const u32*)w.big_list, w.big_cur, w.sorted);
+  return 0;
+}
+
+// the bucket sums of the sorted slab into bucketsX: runs, then the buckets left in pieces (spans), then the heavy ones
+template <class C, int CB>
+static void msm_bucket_sums(ecgpu_ctx* c, const BucketWs<C, CB>& w, size_t cnt) {
+  using X = Xyzz<C>;
+  using J = Jac<C>;
+  const int nb = (int)BucketWs<C, CB>::nb;
+  const u32 ntask = w.ntask;
+  u32 *pieces_ctr = &w.ctr->pieces, *heavy_ctr = &w.ctr->heavy;       // heavy_ctr: the pair heavy, heavy_chunks
+  hipLaunchKernelGGL((bucket_sum_kernel<C, CB>), dim3(ntask / 256), dim3(256), 0, c->stream, (const u32*)w.prep, cnt, (const u32*)w.offsets, (const u32*)w.sorted, nb, ntask,
+                     w.bucketsX, w.head, w.tail, pieces_ctr, w.span_list);
+  hipLaunchKernelGGL((span_combine_kernel<C, CB>), dim3(ecgpu_grid_for(c, ntask, 8)), dim3(256), 0, c->stream, (const u32*)w.offsets, nb, ntask, (const u32*)pieces_ctr,
+                     (const u32*)w.span_list, (const X*)w.head, (const X*)w.tail, w.bucketsX, heavy_ctr, w.heavy, w.chunks);
+  hipLaunchKernelGGL((heavy_chunk_kernel<C, CB>), dim3((unsigned)c->num_cus * 4), dim3(256), 0, c->stream, (const u32*)w.offsets, nb, ntask, (const u32*)heavy_ctr,
+                     (const HeavyChunk*)w.chunks, (const X*)w.head, (const X*)w.tail, w.partial);
+  hipLaunchKernelGGL((heavy_finish_kernel<C>), dim3((unsigned)c->num_cus), dim3(256), 0, c->stream, (const u32*)heavy_ctr, (const HeavyBucket*)w.heavy, (const J*)w.partial,
+                     w.bucketsX);
+}
+
+// buckets -> nb / 8 nodes (-> / 8 for the wide windows) -> groups of 256 nodes -> the NWIN window sums of the slab in wdst
+template <class C, int CB>
+static void msm_reduce_buckets(ecgpu_ctx* c, const BucketWs<C, CB>& w, Jac<C>* wdst) {
+  using G = Geo<CB>;
+  using X = Xyzz<C>;
+  using J = Jac<C>;
   constexpr int NG = G::NG, LOG_NG = G::LOG_NG, TEAM = NG < 64 ? 64 : NG;        // lanes per team of the window kernel: whole waves
-  // a run leaves at most two pieces (head and tail), so there are at most 2 ntask pieces: at most 2 ntask / SPAN_MAX buckets
-  // over more than SPAN_MAX runs, cut into at most 2 ntask / HEAVY_CHUNK + one chunk each
-  const size_t hmax = 2 * (size_t)ntask / SPAN_MAX + 1, cmax = 2 * (size_t)ntask / HEAVY_CHUNK + hmax + 1;
-  // sort bins above BIG_BIN_TILES tiles: at most (entries of a slab) / (entries of such a bin) of them
-  const size_t maxbig = (size_t)NDIG * m / (BIG_BIN_TILES * FineTile<CB>::TILE) + 1;
-  const size_t sz_big = al(maxbig * 4) + 2 * al(maxbig * G::NFINE * 4);
-  const size_t sz_ctr = al(16), sz_heavy = al(hmax * sizeof(HeavyBucket)), sz_chunks = al(cmax * sizeof(HeavyChunk)), sz_partial = al(cmax * sizeof(J));
-  const size_t need = sz_aff + sz_prep + sz_mag + sz_sgn + sz_off + sz_coff + sz_tot + sz_part + 2 * sz_sorted + sz_bx + 2 * sz_piece + sz_span + 2 * sz_l0 + 2 * sz_l1 + sz_grp +
-                      2 * sz_win + sz_ctr + sz_heavy + sz_chunks + sz_partial + sz_big;
-  int rc = ecgpu_reserve(c, c->msm_ws, need);
+  size_t nodes = BucketWs<C, CB>::n0;
+  int log_size = G::LOG_M;
+  J *it = w.ta, *iw = w.wa;
+  hipLaunchKernelGGL((level0_kernel<C, CB>), dim3((unsigned)((nodes + 63) / 64)), dim3(64), 0, c->stream, (const X*)w.bucketsX, (const u32*)w.offsets, w.ta, w.wa, (int)nodes);
+  for (int lv = 0; lv < G::NMID; lv++) {
+    nodes /= G::M;
+    hipLaunchKernelGGL((level_kernel<C, CB>), dim3((unsigned)((nodes + 63) / 64)), dim3(64), 0, c->stream, (const J*)it, (const J*)iw, w.tb, w.wb, log_size, (int)nodes);
+    it = w.tb; iw = w.wb;
+    log_size += G::LOG_M;
+  }
+  hipLaunchKernelGGL((group_kernel<C>), dim3((unsigned)(nodes / GROUP_NODES)), dim3(3 * GROUP_NODES), 0, c->stream, (const J*)it, (const J*)iw, w.grp);
+  hipLaunchKernelGGL((window_kernel<C>), dim3(BucketWs<C, CB>::NWIN), dim3(3 * TEAM), 0, c->stream, (const J*)w.grp, NG, LOG_NG, TEAM, log_size, wdst);
+}
+
+// the bucket method with CB-bit windows: plan, carve, every slab through the three stages, the final Horner pass
+template <class C, int CB>
+static int msm_buckets(ecgpu_ctx* c, const u32* sc, const u32* pts, int pt_fmt, size_t n, u32* out, int out_fmt) {
+  using K = Cfg<C, CB>;
+  using J = Jac<C>;
+  constexpr int NW = C::NW, NWIN = K::NWIN;
+  BucketWs<C, CB> w(c, pt_fmt, n);
+  int rc = ecgpu_carve(c, c->msm_ws, [&](WsCarver& ws) { w.layout(ws); });
   if (rc) return rc;
   // the coarse scatter groups its tiles in more LDS than the 64 KB a kernel gets by default (set per call: the attribute
   // belongs to the function on the current device, and a process may hold contexts on several devices)
   HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&coarse_scatter_kernel<CB>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                 (int)sizeof(typename CoarseTile<CB>::Lds)));
-  char* p = (char*)c->msm_ws.p;
-  u32* aff = (u32*)p; p += sz_aff;
-  u32* prep = (u32*)p; p += sz_prep;
-  Mag* mag = (Mag*)p; p += sz_mag;
-  u32* sgn = (u32*)p; p += sz_sgn;
-  u32* offsets = (u32*)p; p += sz_off;
-  u32* coarse_off = (u32*)p; p += sz_coff;
-  u32* tot = (u32*)p; p += sz_tot;
-  u32* part = (u32*)p; p += sz_part;
-  u32* mid = (u32*)p; p += sz_sorted;
-  u32* sorted = (u32*)p; p += sz_sorted;
-  X* bucketsX = (X*)p; p += sz_bx;
-  X* head = (X*)p; p += sz_piece;
-  X* tail = (X*)p; p += sz_piece;
-  u32* span_list = (u32*)p; p += sz_span;
-  J* ta = (J*)p; p += sz_l0;
-  J* wa = (J*)p; p += sz_l0;
-  J* tb = (J*)p; p += sz_l1;
-  J* wb = (J*)p; p += sz_l1;
-  J* grp = (J*)p; p += sz_grp;
-  J* win = (J*)p; p += sz_win;
-  J* win_slab = (J*)p; p += sz_win;
-  u32* ctr = (u32*)p; p += sz_ctr;                     // [0] buckets in pieces, [1] big sort bins, [2] heavy buckets, [3] heavy chunks
-  HeavyBucket* heavy = (HeavyBucket*)p; p += sz_heavy;
-  HeavyChunk* chunks = (HeavyChunk*)p; p += sz_chunks;
-  J* partial = (J*)p; p += sz_partial;
-  u32* big_cnt = (u32*)p; p += al(maxbig * G::NFINE * 4);          // zeroed together with the list behind it: see the memset below
-  u32* big_list = (u32*)p; p += al(maxbig * 4);
-  u32* big_cur = (u32*)p;
   const size_t pin = (pt_fmt == FMT_PROJECTIVE ? 3 : 2) * (size_t)NW;      // 32-bit words per input point
-  const unsigned cb_grid = (unsigned)((NCB + 255) / 256);
-  for (size_t s0 = 0; s0 < n; s0 += slab) {
-    const size_t cnt = (n - s0 < slab) ? n - s0 : slab;
-    const u32* ssc = sc + s0 * NW;
-    const u32* xy = pts + s0 * pin;
-    if (pt_fmt == FMT_PROJECTIVE) {
-      hipLaunchKernelGGL((to_affine_kernel<C>), dim3(ecgpu_grid_for(c, cnt, 8)), dim3(256), 0, c->stream, xy, aff, cnt);
-      xy = aff;
-    }
-    J* wdst = (s0 == 0) ? win : win_slab;
-    hipLaunchKernelGGL((digits_kernel<C, CB>), dim3(ecgpu_grid_for(c, cnt, 8)), dim3(256), 0, c->stream, ssc, cnt, ms, mag, sgn);
-    hipLaunchKernelGGL((prepare_points_kernel<C>), dim3(ecgpu_grid_for(c, cnt, 8)), dim3(256), 0, c->stream, xy, prep, cnt);
-    hipLaunchKernelGGL((coarse_hist_kernel<CB>), dim3((unsigned)(NWIN * nch)), dim3(1024), 0, c->stream, (const Mag*)mag, cnt, ms, NHALF, nch, part);
-    hipLaunchKernelGGL(coarse_totals_kernel, dim3(cb_grid), dim3(256), 0, c->stream, (const u32*)part, NCB, G::NCOARSE, nch, tot);
-    hipLaunchKernelGGL(coarse_scan_kernel, dim3(1), dim3(1024), 0, c->stream, (const u32*)tot, NCB, coarse_off, offsets + nb);
-    hipLaunchKernelGGL(coarse_cursors_kernel, dim3(cb_grid), dim3(256), 0, c->stream, part, NCB, G::NCOARSE, nch, (const u32*)coarse_off);
-    hipLaunchKernelGGL((coarse_scatter_kernel<CB>), dim3((unsigned)(NWIN * nch)), dim3(1024), sizeof(typename CoarseTile<CB>::Lds), c->stream, (const Mag*)mag, (const u32*)sgn,
-                       cnt, ms, NHALF, CARRY_WIN, nch, (const u32*)part, mid, sorted);
-    HIPCHK(c, hipMemsetAsync(ctr, 0, 16, c->stream));
-    HIPCHK(c, hipMemsetAsync(big_cnt, 0, al(maxbig * G::NFINE * 4), c->stream));
-    hipLaunchKernelGGL((fine_sort_kernel<CB>), dim3((unsigned)NCB), dim3(256), 0, c->stream, (const u32*)mid, (const u32*)coarse_off, CARRY_WIN, offsets, sorted, ctr + 1,
-                       big_list);
-    hipLaunchKernelGGL((big_count_kernel<CB>), dim3((unsigned)c->num_cus * 4), dim3(256), 0, c->stream, (const u32*)mid, (const u32*)coarse_off, (const u32*)(ctr + 1),
-                       (const u32*)big_list, big_cnt);
-    hipLaunchKernelGGL((big_scan_kernel<CB>), dim3(64), dim3(256), 0, c->stream, (const u32*)coarse_off, (const u32*)(ctr + 1), (const u32*)big_list, (const u32*)big_cnt,
-                       big_cur, offsets);
-    hipLaunchKernelGGL((big_place_kernel<CB>), dim3((unsigned)c->num_cus * 4), dim3(256), 0, c->stream, (const u32*)mid, (const u32*)coarse_off, (const u32*)(ctr + 1),
-                       (const u32*)big_list, big_cur, sorted);
-    hipLaunchKernelGGL((bucket_sum_kernel<C, CB>), dim3(ntask / 256), dim3(256), 0, c->stream, (const u32*)prep, cnt, (const u32*)offsets, (const u32*)sorted, (int)nb, ntask,
-                       bucketsX, head, tail, ctr, span_list);
-    hipLaunchKernelGGL((span_combine_kernel<C, CB>), dim3(ecgpu_grid_for(c, ntask, 8)), dim3(256), 0, c->stream, (const u32*)offsets, (int)nb, ntask, (const u32*)ctr,
-                       (const u32*)span_list, (const X*)head, (const X*)tail, bucketsX, ctr + 2, heavy, chunks);
-    hipLaunchKernelGGL((heavy_chunk_kernel<C, CB>), dim3((unsigned)c->num_cus * 4), dim3(256), 0, c->stream, (const u32*)offsets, (int)nb, ntask, (const u32*)(ctr + 2),
-                       (const HeavyChunk*)chunks, (const X*)head, (const X*)tail, partial);
-    hipLaunchKernelGGL((heavy_finish_kernel<C>), dim3((unsigned)c->num_cus), dim3(256), 0, c->stream, (const u32*)(ctr + 2), (const HeavyBucket*)heavy, (const J*)partial,
-                       bucketsX);
-    // buckets -> nb / 8 nodes (-> / 8 for the wide windows) -> groups of 256 nodes -> window sums
-    size_t nodes = n0;
-    int log_size = G::LOG_M;
-    J *it = ta, *iw = wa;
-    hipLaunchKernelGGL((level0_kernel<C, CB>), dim3((unsigned)((nodes + 63) / 64)), dim3(64), 0, c->stream, (const X*)bucketsX, (const u32*)offsets, ta, wa, (int)nodes);
-    for (int lv = 0; lv < G::NMID; lv++) {
-      nodes /= G::M;
-      hipLaunchKernelGGL((level_kernel<C, CB>), dim3((unsigned)((nodes + 63) / 64)), dim3(64), 0, c->stream, (const J*)it, (const J*)iw, tb, wb, log_size, (int)nodes);
-      it = tb; iw = wb;
-      log_size += G::LOG_M;
-    }
-    hipLaunchKernelGGL((group_kernel<C>), dim3((unsigned)(nodes / GROUP_NODES)), dim3(3 * GROUP_NODES), 0, c->stream, (const J*)it, (const J*)iw, grp);
-    hipLaunchKernelGGL((window_kernel<C>), dim3(NWIN), dim3(3 * TEAM), 0, c->stream, (const J*)grp, NG, LOG_NG, TEAM, log_size, wdst);
-    if (s0 != 0) hipLaunchKernelGGL((windows_accumulate_kernel<C>), dim3(1), dim3(64), 0, c->stream, win, (const J*)win_slab, NWIN);
+  for (size_t s0 = 0; s0 < n; s0 += w.slab) {
+    const size_t cnt = (n - s0 < w.slab) ? n - s0 : w.slab;
+    if ((rc = msm_sort_slab(c, w, sc + s0 * NW, pts + s0 * pin, cnt))) return rc;
+    msm_bucket_sums(c, w, cnt);
+    msm_reduce_buckets(c, w, (s0 == 0) ? w.win : w.win_slab);
+    if (s0 != 0) hipLaunchKernelGGL((windows_accumulate_kernel<C>), dim3(1), dim3(64), 0, c->stream, w.win, (const J*)w.win_slab, NWIN);
   }
-  hipLaunchKernelGGL((finish_kernel<C>), dim3(1), dim3(64), 0, c->stream, (const J*)win, (int)NWIN, CB, K::NARROW, out, out_fmt);
+  hipLaunchKernelGGL((finish_kernel<C>), dim3(1), dim3(64), 0, c->stream, (const J*)w.win, (int)NWIN, CB, K::NARROW, out, out_fmt);
   HIPCHK(c, hipGetLastError());
   return 0;
 }
@@ -1184,15 +1245,15 @@ static int msm_run(ecgpu_ctx* c, const u32* sc, const u32* pts, int pt_fmt, size
     return ecgpu_set_err(c, ECGPU_ERR_ARG, "ecgpu_msm: affine device points must be 16-byte aligned for sums of %zu terms and more", (size_t)SMALL_MSM_TERMS);
   if (small) {
     // n scalar multiplications on the throughput kernel, then a two-level sum of the products
-    auto al = msm_align;
     const int blocks = (int)((n + 255) / 256 < 1024 ? (n + 255) / 256 : 1024);
-    const size_t sz_prod = al(n * 8 * NW), sz_part = al((size_t)blocks * sizeof(J)), sz_win = al(sizeof(J));
-    int rc = ecgpu_reserve(c, c->msm_ws, sz_prod + sz_part + sz_win);
+    u32* prod;
+    J *partial, *win;
+    int rc = ecgpu_carve(c, c->msm_ws, [&](WsCarver& ws) {
+      prod = ws.take<u32>(n * 8 * NW);
+      partial = ws.take<J>((size_t)blocks * sizeof(J));
+      win = ws.take<J>(sizeof(J));
+    });
     if (rc) return rc;
-    char* p = (char*)c->msm_ws.p;
-    u32* prod = (u32*)p; p += sz_prod;
-    J* partial = (J*)p; p += sz_part;
-    J* win = (J*)p;
     if ((rc = mul(sc, pts, pt_fmt, prod, n))) return rc;
     hipLaunchKernelGGL((sum_affine_kernel<C>), dim3(blocks), dim3(256), 0, c->stream, (const u32*)prod, n, partial);
     hipLaunchKernelGGL((sum_partials_kernel<C>), dim3(1), dim3(256), 0, c->stream, (const J*)partial, blocks, win);

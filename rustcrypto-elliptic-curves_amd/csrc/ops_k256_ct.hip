@@ -80,11 +80,12 @@ int ecgpuint_k256_reference(ecgpu_ctx* c, const uint32_t* sc, const uint32_t* pt
     size_t blocks = (n + 255) / 256, cap = (size_t)c->num_cus * ECGPU_REF_WAVES, budget = (((size_t)8 << 30) / (per_lane * 256));
     if (blocks > cap) blocks = cap;
     if (blocks > budget) blocks = budget ? budget : 1;
-    const size_t lanes = blocks * 256, sz_tab = (lanes * terms * 16 * sizeof(PtK256) + 255) & ~(size_t)255;
-    int rc = ecgpu_reserve(c, c->tab_ws, sz_tab + lanes * terms * 10 * sizeof(u32));
+    const size_t lanes = blocks * 256;
+    PtK256* tab;
+    u32* naf;
+    int rc = ecgpu_carve(c, c->tab_ws, [&](WsCarver& ws) { tab = ws.take<PtK256>(lanes * terms * 16 * sizeof(PtK256)); naf = ws.take<u32>(lanes * terms * 10 * sizeof(u32)); });
     if (rc) return rc;
-    hipLaunchKernelGGL((k256_lincomb_ref_n_kernel<C>), dim3((unsigned)blocks), dim3(256), 0, c->stream, sc, pts, pt_fmt, (int)terms, out, out_fmt, out_inf, n,
-                       (PtK256*)c->tab_ws.p, (u32*)((char*)c->tab_ws.p + sz_tab));
+    hipLaunchKernelGGL((k256_lincomb_ref_n_kernel<C>), dim3((unsigned)blocks), dim3(256), 0, c->stream, sc, pts, pt_fmt, (int)terms, out, out_fmt, out_inf, n, tab, naf);
   }
   HIPCHK(c, hipGetLastError());
   return 0;

@@ -290,3 +290,47 @@ def test_bucket_path_agrees_with_term_by_term_path_on_awkward_sizes(cn, cid):
                     assert bytes(cv.msm(s, p)) == a, (path, "slabs", n)
     finally:
         ctx.close()
+
+
+def test_one_context_across_workspace_layouts():
+    """The MSM workspace of a context is carved anew by every call, and its layout depends on the path, the term count, the input
+    format and the curve (P-384's 12-word elements change the size of every buffer): one context runs 19-bit windows on 1500
+    terms, 16-bit windows on projective input (the workspace grows), the first call again, then the term-by-term path - on
+    secp256k1, then on P-384 - each against the C oracle, with an identity point and a zero scalar in every input."""
+    import ecgpu
+    ctx = ecgpu.Context(0)
+    try:
+        for cn, cid, n_mid in (("k256", 0, 20000), ("p384", 2, 4096)):
+            c = M.CURVES[cn]
+            nb = c.nbytes
+            cv = ctx.curve(cn)
+            rng = random.Random(90 + cid)
+
+            def case(n, stream):
+                s = CO.synth_scalars(cid, n, synth.SEED, stream)
+                p = CO.synth_points(cid, n, synth.SEED, stream)
+                p[n // 3] = 0
+                s[n // 2] = 0
+                if cid == 0:
+                    w = CO.msm_naive(0, s, p)
+                    assert w[64] == 0
+                    return s, p, bytes(w[:64])
+                w = _oracle_sum(cid, c, s, p)
+                return s, p, M.i2b(c, w[0]) + M.i2b(c, w[1])
+
+            def projective(p):
+                rows = []
+                for r in p:
+                    x, y = int.from_bytes(bytes(r[:nb]), "big"), int.from_bytes(bytes(r[nb:]), "big")
+                    z = rng.randrange(1, c.p)
+                    rows.append(M.proj_bytes(c, M.IDENTITY if x == 0 and y == 0 else (x * z % c.p, y * z % c.p, z)))
+                return arr(rows, 3 * nb)
+
+            first, mid, last = case(1500, 901), case(n_mid, 902), case(300, 903)
+            for path, (s, p, want), fmt in (("buckets19", first, ecgpu.AFFINE), ("buckets16", mid, ecgpu.PROJECTIVE), ("buckets19", first, ecgpu.AFFINE),
+                                            ("auto", last, ecgpu.AFFINE)):
+                _set_path(ctx, path)
+                got = cv.msm(s, projective(p) if fmt == ecgpu.PROJECTIVE else p, point_format=fmt)
+                assert bytes(got) == want, (cn, path, len(s))
+    finally:
+        ctx.close()

@@ -143,6 +143,40 @@ def test_sign_prehash_equals_sign_with_model_nonces(ctx, cn, cid, n):
         assert bytes(t_sig.cpu().numpy()) == bytes(want_sig) and bytes(t_rec.cpu().numpy()) == bytes(want_rec) and bytes(t_ok.cpu().numpy()) == bytes(want_ok)
 
 
+@pytest.mark.parametrize("with_extra", [False, True])
+@pytest.mark.parametrize("cn", ["k256", "p384"])
+def test_sign_prehash_first_call_and_growing_workspace(ctx, cn, with_extra):
+    """ecgpu_ecdsa_sign_prehash_batch as the first call a context ever sees (its workspace does not exist yet), then on a larger
+    batch (the workspace grows between the calls and loses its contents), then on the first batch again: the nonces derived into
+    the workspace reach the signing kernels every time - signature, recovery id and ok equal those of ecgpu_ecdsa_sign_batch
+    (on the module's context) fed the model's nonces"""
+    import ecgpu
+    c = M.CURVES[cn]
+    nb = c.nbytes
+    small = batch(cn, 300, with_extra)[:4]
+    # 5000 rows: the pool's NMAX (with its planted edges), then rows of a generator of their own
+    d, z, x, k, _ = batch(cn, NMAX, with_extra)
+    rng = random.Random(0x6A0 + nb + with_extra)
+    td = [rng.randrange(1, c.n) for _ in range(5000 - NMAX)]
+    tz = [rng.randbytes(nb) for _ in td]
+    tx = [rng.randbytes(nb) for _ in td]
+    tk = [R.nonce(c, td[i], tz[i], tx[i] if with_extra else b"") for i in range(len(td))]
+    large = (np.concatenate([d, _rows(td, nb)]), np.concatenate([z, _rows(tz, nb)]), np.concatenate([x, _rows(tx, nb)]) if with_extra else None,
+             np.concatenate([k, _rows(tk, nb)]))
+    want = [ctx.curve(cn).ecdsa_sign(bd, bk, bz) for bd, bz, _, bk in (small, large)]
+    fresh = ecgpu.Context(0)
+    try:
+        cv = fresh.curve(cn)
+        assert fresh.debug_workspace(1) == b""
+        for (bd, bz, bx, _), w in ((small, want[0]), (large, want[1]), (small, want[0])):
+            got = cv.ecdsa_sign_prehash(bd, bz, bx)
+            for a, b in zip(got, w):
+                assert bytes(a) == bytes(b), (cn, with_extra, len(bd))
+            assert got[2].sum() == len(bd) - 3        # the three invalid keys batch() plants
+    finally:
+        fresh.close()
+
+
 @pytest.mark.parametrize("cn,cid", CURVES)
 def test_sign_prehash_flags(ctx, cn, cid):
     import ecgpu
