@@ -37,6 +37,14 @@ static constexpr u32 C_LO = 977;   // C = 2^32 + C_LO
 #else
 #define ECGPU_K256_RARE(cond) __builtin_expect((cond), 0)
 #endif
+// The products (mul, mul_add2, mul_add_sqr, sqr) with every carry addition and no branch on a carry: the branch-free build, and a
+// translation unit that defines ECGPU_K256_EXACT_PRODUCTS (msm_k256.hip: its kernels measured slower with the speculative columns
+// below, profiles/spec_carry.txt).
+#if defined(ECGPU_K256_BRANCHFREE) || defined(ECGPU_K256_EXACT_PRODUCTS)
+#define ECGPU_K256_SPEC_PRODUCTS 0
+#else
+#define ECGPU_K256_SPEC_PRODUCTS 1
+#endif
 
 // r += T * C for a small T (< 2^40), then fold the possible carry out of 2^256 once more.
 ECGPU_HD void fold_top(u32* r, u64 T) {
@@ -114,7 +122,7 @@ ECGPU_HD void mul_low_column(u32* t, Acc96& c, const u32* a, const u32* b, const
   mac_product_column<8, K, 1, true, 1>(c, a, b, xa, xb);      // h[K] * 977 first: < 2^43 with the carry-in (nc_bound)
   t[K] = acc_pop(c);
 }
-ECGPU_HD void mul(FeK256& r, const FeK256& a, const FeK256& b) {
+ECGPU_HD void mul_exact(FeK256& r, const FeK256& a, const FeK256& b) {
   u32 h[8], t[8];
   Acc96 c{0, 0};
   mul_high_column<8>(h, c, a.v, b.v);  mul_high_column<9>(h, c, a.v, b.v);
@@ -136,6 +144,91 @@ ECGPU_HD void mul(FeK256& r, const FeK256& a, const FeK256& b) {
   fold_top_fast(r.v, T);
 }
 
+// Speculative products (SPEC; ECGPU_K256_SPEC_PRODUCTS: the throughput build of the variable-base and signature kernels).  After its no-carry products a column starts
+// below 2^43 (low half) or 2^38 (high half: a popped carry, + s_i * d_8 in mul_add_sqr), and its next product is at most
+// 2^64 - 2^33 + 1: adding it carries out of c.lo only when the product exceeds 2^64 - 2^43, probability about 2^-43 (2^-55 in the
+// high half) for uniform limbs.  That product goes in WITHOUT its carry addition (mac_colM_nN_s1): the mad's carry-out lane mask is
+// kept in scalar registers, and a wave-uniform branch - the policy of ECGPU_K256_RARE, taken when any lane's bit is set - adds
+// the missing carry to c.hi before the column is popped (mp32.hpp: mac_cols with SPEC).  One VALU carry addition less per column,
+// a scalar compare and branch instead: 12 in mul (and column 14 without any) and in mul_add2, 14 in mul_add_sqr, 5 in sqr (and 8
+// more without any).  A column whose only carry addition would go stays exact (low column 0 of mul and mul_add2, high column 14 of mul_add2): that addition
+// creates c.hi, and a move would have to take its place.  The bounds below say how rare the branch is; the value never depends on
+// them.  The *_exact bodies (every product with its carry addition, no such branch) are the products of the other builds.
+//  - high column 14 of mul is the single product a_7 b_7 on the carry popped from column 13; even for all-ones operands (every
+//    column sum is monotone in the limbs) it does not carry: a no-carry product, not a speculative one.  Not so with a second
+//    product in the column (mul_add2, mul_add_sqr).
+//  - the squaring's cross columns 1 to 5 and 11 to 13 cannot carry at their first product even for an all-ones operand: no-carry
+//    products (mp32.hpp: sqr_cross_first_nc, mp_sqr_wide with SPEC); those of one product (1, 2, 12, 13) are plain C++.
+namespace nc_bound {
+// carry popped into high column K of an 8 x 8 product of all-ones operands (the high half starts from zero at column 8)
+constexpr u128 high_carry_in(int K) {
+  u128 c = 0;
+  for (int k = 8; k < K; k++) c = (c + (u128)(15 - k) * MAX_PRODUCT) >> 32;
+  return c;
+}
+static_assert(high_carry_in(14) + MAX_PRODUCT < ((u128)1 << 64), "mul, high column 14: a_7 b_7 on the popped carry cannot carry");
+static_assert(2 * high_carry_in(14) + 1 + MAX_PRODUCT >= ((u128)1 << 64), "with two products per column (mul_add2) it can: speculative there");
+static_assert(((u128)1 << 43) + MAX_PRODUCT >= ((u128)1 << 64) && MAX_PRODUCT == ((u128)1 << 64) - ((u128)1 << 33) + 1,
+              "low half: the speculative product starts below 2^43 and carries only for a product above 2^64 - 2^43");
+static_assert(((u128)1 << 37) + 0xFFFFFFFFu < ((u128)1 << 38), "high half: the speculative product starts below 2^38 (popped carry, + s_i d_8 in mul_add_sqr)");
+}  // namespace nc_bound
+#if !ECGPU_K256_SPEC_PRODUCTS
+ECGPU_HD void mul(FeK256& r, const FeK256& a, const FeK256& b) { mul_exact(r, a, b); }
+#else
+template <int K>
+ECGPU_HD void mul_high_column_spec(u32* h, Acc96& c, const u32* a, const u32* b, u64& raised) {
+  static_assert(K >= 9 && K <= 14, "column 8 starts from zero and stays mul_high_column<8>");
+  if constexpr (K == 14) {
+    mac_nc(c, a[7], b[7]);                  // nc_bound: high_carry_in(14); c.hi stays zero, so the two words of c.lo are h[6] and h[7]
+    h[6] = (u32)c.lo;
+    c.lo >>= 32;
+    return;
+  } else {
+    u64 k = 0;
+    mac_product_column<8, K, 0, true, 0, true>(c, a, b, nullptr, nullptr, k);
+    ECGPU_SPEC_NOTE("mul", K, k != 0);
+    raised |= k;
+  }
+  h[K - 8] = acc_pop(c);
+}
+template <int K>
+ECGPU_HD void mul_low_column_spec(u32* t, Acc96& c, const u32* a, const u32* b, const u32* h, u64& raised) {
+  static_assert(K >= 1 && K <= 7, "column 0 has one product after the fold term, whose carry addition creates c.hi: it stays mul_low_column<0>");
+  const u32 xa[1] = {h[K]}, xb[1] = {C_LO};
+  u64 k = 0;
+  mac_product_column<8, K, 1, true, 1, true>(c, a, b, xa, xb, k);      // h[K] * 977 without a carry, then a_0 b_K speculative
+  ECGPU_SPEC_NOTE("mul", K, k != 0);
+  raised |= k;
+  t[K] = acc_pop(c);
+}
+// the tail of the three products: H * 2^32 (the other half of H * C) is one carry chain; its top word joins the overflow above 2^256.
+// h8: word 16 of a sum of two products (0 or 1), handled as in mul_add2_exact.
+ECGPU_HD void mul_finish(FeK256& r, const u32* t, const u32* h, const Acc96& c, u32 h8) {
+  u32 cy = 0;
+  r.v[0] = t[0];
+#pragma unroll
+  for (int i = 1; i < 8; i++) r.v[i] = addc(t[i], h[i - 1], cy);
+  const u64 T = c.lo + h[7] + cy + (((u64)h8 << 32) | (h8 ? C_LO : 0u));     // < 2^38
+  fold_top_fast(r.v, T);
+}
+ECGPU_HD void mul(FeK256& r, const FeK256& a, const FeK256& b) {
+  u32 h[8], t[8];
+  u64 raised = 0;
+  Acc96 c{0, 0};
+  mul_high_column<8>(h, c, a.v, b.v);
+  mul_high_column_spec<9>(h, c, a.v, b.v, raised);  mul_high_column_spec<10>(h, c, a.v, b.v, raised);
+  mul_high_column_spec<11>(h, c, a.v, b.v, raised); mul_high_column_spec<12>(h, c, a.v, b.v, raised);
+  mul_high_column_spec<13>(h, c, a.v, b.v, raised); mul_high_column_spec<14>(h, c, a.v, b.v, raised);
+  h[7] = (u32)c.lo;
+  c.lo = 0; c.hi = 0;
+  mul_low_column<0>(t, c, a.v, b.v, h); mul_low_column_spec<1>(t, c, a.v, b.v, h, raised);
+  mul_low_column_spec<2>(t, c, a.v, b.v, h, raised); mul_low_column_spec<3>(t, c, a.v, b.v, h, raised);
+  mul_low_column_spec<4>(t, c, a.v, b.v, h, raised); mul_low_column_spec<5>(t, c, a.v, b.v, h, raised);
+  mul_low_column_spec<6>(t, c, a.v, b.v, h, raised); mul_low_column_spec<7>(t, c, a.v, b.v, h, raised);
+  mul_finish(r, t, h, c, 0);
+}
+#endif
+
 // r = a * b + e * f mod p (weakly reduced): both products ride on the same column accumulators and share ONE reduction (the
 // point formulas end in differences of two products: Y3 = R (V - X3) - Y1 HHH).  A column holds up to 16 products plus the
 // fold term, < 2^69: the 96-bit accumulator has room.  The sum of the two products can reach 2^513, so word 16 (one bit) exists:
@@ -154,7 +247,7 @@ ECGPU_HD void mul2_low_column(u32* t, Acc96& c, const u32* a, const u32* b, cons
   mac_product_column<8, K, 0, false>(c, e, f, nullptr, nullptr);
   t[K] = acc_pop(c);
 }
-ECGPU_HD void mul_add2(FeK256& r, const FeK256& a, const FeK256& b, const FeK256& e, const FeK256& f) {
+ECGPU_HD void mul_add2_exact(FeK256& r, const FeK256& a, const FeK256& b, const FeK256& e, const FeK256& f) {
   u32 h[8], t[8];
   Acc96 c{0, 0};
   mul2_high_column<8>(h, c, a.v, b.v, e.v, f.v);  mul2_high_column<9>(h, c, a.v, b.v, e.v, f.v);
@@ -175,6 +268,49 @@ ECGPU_HD void mul_add2(FeK256& r, const FeK256& a, const FeK256& b, const FeK256
   const u64 T = c.lo + h[7] + cy + (((u64)h8 << 32) | (h8 ? C_LO : 0u));     // < 2^38
   fold_top_fast(r.v, T);
 }
+
+#if !ECGPU_K256_SPEC_PRODUCTS
+ECGPU_HD void mul_add2(FeK256& r, const FeK256& a, const FeK256& b, const FeK256& e, const FeK256& f) { mul_add2_exact(r, a, b, e, f); }
+#else
+template <int K>
+ECGPU_HD void mul2_high_column_spec(u32* h, Acc96& c, const u32* a, const u32* b, const u32* e, const u32* f, u64& raised) {
+  static_assert(K >= 9 && K <= 13, "column 8 starts from zero; column 14 has one product a_7 b_7, whose carry addition creates c.hi");
+  u64 k = 0;
+  mac_product_column<8, K, 0, true, 0, true>(c, a, b, nullptr, nullptr, k);
+  ECGPU_SPEC_NOTE("mul_add2", K, k != 0);
+  raised |= k;
+  mac_product_column<8, K, 0, false>(c, e, f, nullptr, nullptr);
+  h[K - 8] = acc_pop(c);
+}
+template <int K>
+ECGPU_HD void mul2_low_column_spec(u32* t, Acc96& c, const u32* a, const u32* b, const u32* e, const u32* f, const u32* h, u64& raised) {
+  static_assert(K >= 1 && K <= 7, "column 0 stays mul2_low_column<0>, as in mul");
+  const u32 xa[1] = {h[K]}, xb[1] = {C_LO};
+  u64 k = 0;
+  mac_product_column<8, K, 1, true, 1, true>(c, a, b, xa, xb, k);
+  ECGPU_SPEC_NOTE("mul_add2", K, k != 0);
+  raised |= k;
+  mac_product_column<8, K, 0, false>(c, e, f, nullptr, nullptr);
+  t[K] = acc_pop(c);
+}
+ECGPU_HD void mul_add2(FeK256& r, const FeK256& a, const FeK256& b, const FeK256& e, const FeK256& f) {
+  u32 h[8], t[8];
+  u64 raised = 0;
+  Acc96 c{0, 0};
+  mul2_high_column<8>(h, c, a.v, b.v, e.v, f.v);
+  mul2_high_column_spec<9>(h, c, a.v, b.v, e.v, f.v, raised);  mul2_high_column_spec<10>(h, c, a.v, b.v, e.v, f.v, raised);
+  mul2_high_column_spec<11>(h, c, a.v, b.v, e.v, f.v, raised); mul2_high_column_spec<12>(h, c, a.v, b.v, e.v, f.v, raised);
+  mul2_high_column_spec<13>(h, c, a.v, b.v, e.v, f.v, raised); mul2_high_column<14>(h, c, a.v, b.v, e.v, f.v);
+  h[7] = (u32)c.lo;
+  const u32 h8 = (u32)(c.lo >> 32);                 // word 16 of the sum: 0 or 1
+  c.lo = 0; c.hi = 0;
+  mul2_low_column<0>(t, c, a.v, b.v, e.v, f.v, h); mul2_low_column_spec<1>(t, c, a.v, b.v, e.v, f.v, h, raised);
+  mul2_low_column_spec<2>(t, c, a.v, b.v, e.v, f.v, h, raised); mul2_low_column_spec<3>(t, c, a.v, b.v, e.v, f.v, h, raised);
+  mul2_low_column_spec<4>(t, c, a.v, b.v, e.v, f.v, h, raised); mul2_low_column_spec<5>(t, c, a.v, b.v, e.v, f.v, h, raised);
+  mul2_low_column_spec<6>(t, c, a.v, b.v, e.v, f.v, h, raised); mul2_low_column_spec<7>(t, c, a.v, b.v, e.v, f.v, h, raised);
+  mul_finish(r, t, h, c, h8);
+}
+#endif
 
 // Column K of s^2 with the cross products already doubled: s^2 = sum_i s_i^2 B^2i + sum_{i <= 6} s_i B^i T_i, B = 2^32, where
 // T_i = 2 sum_{j > i} s_j B^j has the words e_(i+1) = s_(i+1) << 1 at B^(i+1) and d_j = (s_j << 1) | (s_(j-1) >> 31) at B^j for
@@ -240,7 +376,7 @@ ECGPU_HD void mulsq_low_column(u32* t, Acc96& c, const u32* a, const u32* b, con
 }
 // r = a * b + s^2 mod p (weakly reduced): mul_add2 with a square as its second product (the doubling's Y3).  The sum is < 2^513, so
 // word 16 is handled as in mul_add2.
-ECGPU_HD void mul_add_sqr(FeK256& r, const FeK256& a, const FeK256& b, const FeK256& s) {
+ECGPU_HD void mul_add_sqr_exact(FeK256& r, const FeK256& a, const FeK256& b, const FeK256& s) {
   u32 e[8], d[9], h[8], t[8];
   e[0] = 0; d[0] = 0; d[1] = 0;
   sqr2_operands(e, d, s.v);
@@ -264,6 +400,62 @@ ECGPU_HD void mul_add_sqr(FeK256& r, const FeK256& a, const FeK256& b, const FeK
   fold_top_fast(r.v, T);
 }
 
+#if !ECGPU_K256_SPEC_PRODUCTS
+ECGPU_HD void mul_add_sqr(FeK256& r, const FeK256& a, const FeK256& b, const FeK256& s) { mul_add_sqr_exact(r, a, b, s); }
+#else
+// mulsq_column with the product after its NC no-carry ones speculative
+template <int K, int NX, int NC>
+ECGPU_HD void mulsq_column_spec(Acc96& c, const u32* a, const u32* b, const u32* s, const u32* e, const u32* d, const u32* xa, const u32* xb, u64& raised) {
+  constexpr int LO = (K - 7) > 0 ? (K - 7) : 0;
+  constexpr int HI = K < 7 ? K : 7;
+  constexpr int M = HI - LO + 1;
+  constexpr int MS = sqr2_terms(K);
+  constexpr int D8 = sqr2_has_d8(K) ? 1 : 0;
+  u32 pa[M + MS + NX + 1], pb[M + MS + NX + 1];
+#pragma unroll
+  for (int m = 0; m < NX; m++) { pa[m] = xa[m]; pb[m] = xb[m]; }
+  if constexpr (D8) { pa[NX] = s[K - 8]; pb[NX] = d[8]; }
+#pragma unroll
+  for (int m = 0; m < M; m++) { pa[NX + D8 + m] = a[LO + m]; pb[NX + D8 + m] = b[K - LO - m]; }
+  sqr2_column_terms<K>(pa + NX + D8 + M, pb + NX + D8 + M, s, e, d);
+  u64 k = 0;
+  mac_cols<M + MS + NX, true, NC, true>(c, pa, pb, k);
+  ECGPU_SPEC_NOTE("mul_add_sqr", K, k != 0);
+  raised |= k;
+}
+template <int K>
+ECGPU_HD void mulsq_high_column_spec(u32* h, Acc96& c, const u32* a, const u32* b, const u32* s, const u32* e, const u32* d, u64& raised) {
+  static_assert(K >= 9 && K <= 14, "column 8 starts from zero and stays mulsq_high_column<8>");
+  mulsq_column_spec<K, 0, 1>(c, a, b, s, e, d, nullptr, nullptr, raised);     // s_(K-8) d_8 without a carry, then a_(K-7) b_7 speculative
+  h[K - 8] = acc_pop(c);
+}
+template <int K>
+ECGPU_HD void mulsq_low_column_spec(u32* t, Acc96& c, const u32* a, const u32* b, const u32* s, const u32* e, const u32* d, const u32* h, u64& raised) {
+  const u32 xa[1] = {h[K]}, xb[1] = {C_LO};
+  mulsq_column_spec<K, 1, 1>(c, a, b, s, e, d, xa, xb, raised);
+  t[K] = acc_pop(c);
+}
+ECGPU_HD void mul_add_sqr(FeK256& r, const FeK256& a, const FeK256& b, const FeK256& s) {
+  u32 e[8], d[9], h[8], t[8];
+  e[0] = 0; d[0] = 0; d[1] = 0;
+  sqr2_operands(e, d, s.v);
+  u64 raised = 0;
+  Acc96 c{0, 0};
+  mulsq_high_column<8>(h, c, a.v, b.v, s.v, e, d);
+  mulsq_high_column_spec<9>(h, c, a.v, b.v, s.v, e, d, raised);  mulsq_high_column_spec<10>(h, c, a.v, b.v, s.v, e, d, raised);
+  mulsq_high_column_spec<11>(h, c, a.v, b.v, s.v, e, d, raised); mulsq_high_column_spec<12>(h, c, a.v, b.v, s.v, e, d, raised);
+  mulsq_high_column_spec<13>(h, c, a.v, b.v, s.v, e, d, raised); mulsq_high_column_spec<14>(h, c, a.v, b.v, s.v, e, d, raised);
+  h[7] = (u32)c.lo;
+  const u32 h8 = (u32)(c.lo >> 32);                 // word 16 of the sum: 0 or 1
+  c.lo = 0; c.hi = 0;
+  mulsq_low_column_spec<0>(t, c, a.v, b.v, s.v, e, d, h, raised); mulsq_low_column_spec<1>(t, c, a.v, b.v, s.v, e, d, h, raised);
+  mulsq_low_column_spec<2>(t, c, a.v, b.v, s.v, e, d, h, raised); mulsq_low_column_spec<3>(t, c, a.v, b.v, s.v, e, d, h, raised);
+  mulsq_low_column_spec<4>(t, c, a.v, b.v, s.v, e, d, h, raised); mulsq_low_column_spec<5>(t, c, a.v, b.v, s.v, e, d, h, raised);
+  mulsq_low_column_spec<6>(t, c, a.v, b.v, s.v, e, d, h, raised); mulsq_low_column_spec<7>(t, c, a.v, b.v, s.v, e, d, h, raised);
+  mul_finish(r, t, h, c, h8);
+}
+#endif
+
 // reduce a 16-word integer modulo p: lo + hi * 977 + (hi << 32), then fold what spills over 2^256
 ECGPU_HD void reduce16(FeK256& r, const u32* w) {
   u32 u[8];
@@ -285,10 +477,22 @@ ECGPU_HD void reduce16(FeK256& r, const u32* w) {
 }
 
 // r = a^2 mod p
-ECGPU_HD void sqr(FeK256& r, const FeK256& a) {
+ECGPU_HD void sqr_exact(FeK256& r, const FeK256& a) {
   u32 w[16];
   mp_sqr_wide<8>(w, a.v);
   reduce16(r, w);
+}
+
+// the cross columns speculative (mp_sqr_wide with SPEC; its hook reports site "sqr")
+ECGPU_HD void sqr(FeK256& r, const FeK256& a) {
+#if !ECGPU_K256_SPEC_PRODUCTS
+  sqr_exact(r, a);
+#else
+  u32 w[16];
+  u64 raised = 0;
+  mp_sqr_wide<8, true>(w, a.v, raised);
+  reduce16(r, w);
+#endif
 }
 
 // r = a + b mod p   (field_5x52.rs:264-272 adds limb-wise and defers; here the fold is immediate).

@@ -42,6 +42,12 @@
 #ifndef ECGPU_EXC_NOTE
 #define ECGPU_EXC_NOTE(site, cond) ((void)0)
 #endif
+// Hook at every speculative product of the k256 field products (fe_k256.hpp), after its column (the missing carry already added) and
+// before its carry-out flag is merged with the others: empty in the product, and `raised` is NOT evaluated there.  The test-only host build records, per site name
+// and column, whether the flag was raised, which is how the tests show that their inputs reach every rare carry branch.
+#ifndef ECGPU_SPEC_NOTE
+#define ECGPU_SPEC_NOTE(site, column, raised) ((void)0)
+#endif
 
 namespace ecgpu {
 
@@ -154,6 +160,22 @@ ECGPU_HD void mac(Acc96& c, u32 a, u32 b) {
 }
 // c += a * b where the caller guarantees the low 64 bits cannot overflow
 ECGPU_HD void mac_nc(Acc96& c, u32 a, u32 b) { c.lo += (u64)a * b; }
+// c.lo += a * b WITHOUT the carry into c.hi; returns whether the low 64 bits wrapped (portable twin of the speculative product of the
+// mac_colM_nN_s1 forms, whose device form returns the mad's carry-out lane mask).  mac_spec_fix adds what it returns.
+ECGPU_HD u64 mac_spec(Acc96& c, u32 a, u32 b) {
+  const u64 p = (u64)a * b;
+  c.lo += p;
+  return c.lo < p ? 1u : 0u;
+}
+// c.hi += the carry that a speculative product left in k (device: a lane mask, the carry-in of one v_addc_co_u32).  Additions
+// commute, so it may come after the column's other products; it must come before the accumulator is popped.
+ECGPU_HD void mac_spec_fix(Acc96& c, u64 k) {
+#if ECGPU_ASM
+  asm("v_addc_co_u32 %0, vcc, 0, %0, %1" : "+v"(c.hi) : "s"(k) : "vcc");
+#else
+  c.hi += (u32)k;
+#endif
+}
 // c -= w, the accumulator read as a 96-bit two's-complement number
 ECGPU_HD void acc_sub32(Acc96& c, u32 w) {
   u32 l0 = (u32)c.lo, l1 = (u32)(c.lo >> 32), bw = 0;
@@ -193,6 +215,28 @@ ECGPU_HD void mac_cols(Acc96& c, const u32* pa, const u32* pb) {
     if constexpr (M == 12) { if constexpr (FRESH) mac_col12_f(c, pa[0], pb[0], pa[1], pb[1], pa[2], pb[2], pa[3], pb[3], pa[4], pb[4], pa[5], pb[5], pa[6], pb[6], pa[7], pb[7], pa[8], pb[8], pa[9], pb[9], pa[10], pb[10], pa[11], pb[11]); else mac_col12(c, pa[0], pb[0], pa[1], pb[1], pa[2], pb[2], pa[3], pb[3], pa[4], pb[4], pa[5], pb[5], pa[6], pb[6], pa[7], pb[7], pa[8], pb[8], pa[9], pb[9], pa[10], pb[10], pa[11], pb[11]); }
   }
 }
+// The same with SPEC: after the NC products comes one SPECULATIVE product (mac_colM_nN_s1).  It starts from an accumulator so small
+// (the caller's bound) that its carry out of c.lo is rarer than 2^-40, so the column issues it WITHOUT its carry addition and keeps the
+// mad's carry-out lane mask in a scalar-register pair; a wave-uniform branch, almost never taken, adds the missing carry when any
+// lane's bit is set.  The value is exact either way; which way the branch goes depends on the data (not for secret inputs).  The mask
+// (0 or 1 in the portable build) is OR-ed into `raised` for the caller's ECGPU_SPEC_NOTE.  Without SPEC this is mac_cols above.
+template <int M, bool FRESH = false, int NC = 0, bool SPEC = false>
+ECGPU_HD void mac_cols(Acc96& c, const u32* pa, const u32* pb, u64& raised) {
+  if constexpr (!SPEC) {
+    mac_cols<M, FRESH, NC>(c, pa, pb);
+  } else {
+    static_assert(M >= 1 && NC >= 0 && NC <= 2 && NC + 1 <= M, "the speculative product follows the no-carry products");
+    u64 k;
+    if constexpr (M > 12) {
+      mac_cols_s1<12, FRESH, NC>(c, k, pa, pb);
+      mac_cols<M - 12, false>(c, pa + 12, pb + 12);
+    } else {
+      mac_cols_s1<M, FRESH, NC>(c, k, pa, pb);
+    }
+    if (__builtin_expect(k != 0, 0)) mac_spec_fix(c, k);
+    raised |= k;
+  }
+}
 // column k of the N x N schoolbook product: sum_{i+j=k} a_i b_j, plus NX extra products (xa, xb) issued FIRST, so that a
 // small extra product (the k256 fold term) can go in without a carry.  NC: the first NC products of that order (extras, then
 // a_LO b_(k-LO), ..) cannot carry out of c.lo, as the caller states.
@@ -207,6 +251,19 @@ ECGPU_HD void mac_product_column(Acc96& c, const u32* a, const u32* b, const u32
 #pragma unroll
   for (int m = 0; m < M; m++) { pa[NX + m] = a[LO + m]; pb[NX + m] = b[K - LO - m]; }
   mac_cols<M + NX, FRESH, NC>(c, pa, pb);
+}
+// SPEC: the product after the NC leading ones is speculative (mac_cols with `raised`)
+template <int N, int K, int NX, bool FRESH = false, int NC = 0, bool SPEC = false>
+ECGPU_HD void mac_product_column(Acc96& c, const u32* a, const u32* b, const u32* xa, const u32* xb, u64& raised) {
+  constexpr int LO = (K - (N - 1)) > 0 ? (K - (N - 1)) : 0;
+  constexpr int HI = K < (N - 1) ? K : (N - 1);
+  constexpr int M = HI - LO + 1;
+  u32 pa[M + NX + 1], pb[M + NX + 1];
+#pragma unroll
+  for (int m = 0; m < NX; m++) { pa[m] = xa[m]; pb[m] = xb[m]; }
+#pragma unroll
+  for (int m = 0; m < M; m++) { pa[NX + m] = a[LO + m]; pb[NX + m] = b[K - LO - m]; }
+  mac_cols<M + NX, FRESH, NC, SPEC>(c, pa, pb, raised);
 }
 
 // pop the low word and shift the accumulator down by 32 bits
@@ -266,6 +323,53 @@ ECGPU_HD void sqr_cross_columns(u32* x, Acc96& c, const u32* a) {
   }
 }
 
+// Whether the first product of cross column K of an N-word square cannot carry out of c.lo: the carry popped into the column for an
+// all-ones operand (every column sum is monotone in the words) plus the largest product stays below 2^64.
+template <int N>
+constexpr bool sqr_cross_first_nc(int K) {
+  typedef unsigned __int128 u128;
+  const u128 maxp = (u128)0xFFFFFFFFu * 0xFFFFFFFFu;
+  u128 c = 0;
+  for (int k = 1; k < K; k++) {
+    const int lo = (k - (N - 1)) > 0 ? (k - (N - 1)) : 0, hi = (k - 1) / 2;
+    c = (c + (u128)(hi - lo + 1) * maxp) >> 32;
+  }
+  return c + maxp < ((u128)1 << 64);
+}
+// SPEC: the first product of a cross column is a no-carry product where sqr_cross_first_nc proves it (for N = 8: columns 1 to 5 and
+// 11 to 13) and, in a column of two or more products, speculative elsewhere (mac_cols with `raised`).  A one-product column that is
+// carry-free is written in C++ (mac_nc): the compiler's three-address mad takes the popped word from a pair with a standing zero,
+// one move less than the asm column.  A one-product column that may carry (none for N = 8) stays exact: its carry addition is
+// what creates c.hi, and without it a move would have to.
+static_assert(sqr_cross_first_nc<8>(1) && sqr_cross_first_nc<8>(2) && sqr_cross_first_nc<8>(3) && sqr_cross_first_nc<8>(4) && sqr_cross_first_nc<8>(5) &&
+              !sqr_cross_first_nc<8>(6) && !sqr_cross_first_nc<8>(10) && sqr_cross_first_nc<8>(11) && sqr_cross_first_nc<8>(12) && sqr_cross_first_nc<8>(13),
+              "the carry-free cross columns of the 8-word square, as the comments and tests/k256_spec_carry_vectors.py list them");
+template <int N, int K, bool SPEC>
+ECGPU_HD void mac_cross_column(Acc96& c, const u32* a, u64& raised) {
+  constexpr int LO = (K - (N - 1)) > 0 ? (K - (N - 1)) : 0;
+  constexpr int HI = (K - 1) / 2;
+  constexpr int M = HI - LO + 1;
+  if constexpr (M >= 1) {
+    u32 pa[M], pb[M];
+#pragma unroll
+    for (int m = 0; m < M; m++) { pa[m] = a[LO + m]; pb[m] = a[K - LO - m]; }
+    if constexpr (SPEC && M == 1 && sqr_cross_first_nc<N>(K)) mac_nc(c, pa[0], pb[0]);     // plain C++: a three-address mad, c.hi stays zero
+    else if constexpr (SPEC && M >= 2 && sqr_cross_first_nc<N>(K)) mac_cols<M, true, 1>(c, pa, pb);
+    else mac_cols<M, true, 0, (SPEC && M >= 2)>(c, pa, pb, raised);
+  }
+}
+template <int N, int K, bool SPEC>
+ECGPU_HD void sqr_cross_columns(u32* x, Acc96& c, const u32* a, u64& raised) {
+  if constexpr (K < 2 * N - 2) {
+    u64 k = 0;
+    mac_cross_column<N, K, SPEC>(c, a, k);
+    if constexpr (SPEC && (K - 1) / 2 - ((K - (N - 1)) > 0 ? (K - (N - 1)) : 0) + 1 >= 2 && !sqr_cross_first_nc<N>(K)) { ECGPU_SPEC_NOTE("sqr", K, k != 0); }
+    raised |= k;
+    x[K] = acc_pop(c);
+    sqr_cross_columns<N, K + 1, SPEC>(x, c, a, raised);
+  }
+}
+
 // r[0..2N) = a * a : off-diagonal products once, doubled by a one-bit funnel shift, plus the squares
 template <int N>
 ECGPU_HD void mp_sqr_wide(u32* r, const u32* a) {
@@ -273,6 +377,26 @@ ECGPU_HD void mp_sqr_wide(u32* r, const u32* a) {
   Acc96 c{0, 0};
   x[0] = 0;
   sqr_cross_columns<N, 1>(x, c, a);
+  x[2 * N - 2] = (u32)c.lo;   // the cross sum is < 2^(64N-1): it fits, top bit clear
+  x[2 * N - 1] = (u32)(c.lo >> 32);
+  // r = 2*x + sum a_i^2 2^(64 i)
+  u32 carry = 0;
+#pragma unroll
+  for (int i = 0; i < N; i++) {
+    const u64 d = (u64)a[i] * a[i];
+    const u32 lo2 = (x[2 * i] << 1) | (i ? (x[2 * i - 1] >> 31) : 0);
+    const u32 hi2 = (x[2 * i + 1] << 1) | (x[2 * i] >> 31);
+    r[2 * i] = addc(lo2, (u32)d, carry);
+    r[2 * i + 1] = addc(hi2, (u32)(d >> 32), carry);
+  }
+}
+// the same with speculative cross columns (SPEC); `raised` collects their flags
+template <int N, bool SPEC>
+ECGPU_HD void mp_sqr_wide(u32* r, const u32* a, u64& raised) {
+  u32 x[2 * N];
+  Acc96 c{0, 0};
+  x[0] = 0;
+  sqr_cross_columns<N, 1, SPEC>(x, c, a, raised);
   x[2 * N - 2] = (u32)c.lo;   // the cross sum is < 2^(64N-1): it fits, top bit clear
   x[2 * N - 1] = (u32)(c.lo >> 32);
   // r = 2*x + sum a_i^2 2^(64 i)

@@ -1,4 +1,7 @@
 // Pippenger MSM for k256: msm_kernels.hpp instantiated in its own translation unit (the library builds in parallel).
+// ECGPU_K256_EXACT_PRODUCTS: the bucket kernels keep the field products with every carry addition (fe_k256.hpp).  With the speculative
+// columns the 2^23-pair MSM measured about 3 % slower (profiles/spec_carry.txt), while the variable-base kernels gain.
+#define ECGPU_K256_EXACT_PRODUCTS 1
 #include "msm_kernels.hpp"
 using namespace ecgpu;
 int ecgpu_msm_k256(ecgpu_ctx* c, const uint32_t* sc, const uint32_t* pts, int pt_fmt, size_t n, uint32_t* out, int out_fmt, ecgpu_msm_mul_fn mul) {
