@@ -190,8 +190,9 @@ int ecgpu_host_free(ecgpu_ctx* ctx, void* p);
 int ecgpu_host_chunk_schedule(size_t n, size_t pass_units, size_t* sizes, size_t cap);
 
 /* Diagnostic: size and contents of a context's grow-only device workspaces (which = 0: per-lane table workspace of the
- * variable-base kernels, 1: intermediate scalars / points of the ECDSA / ECDH / hash pipelines, 2: MSM workspace, 3: BIP340 challenges, 16 + i: staging slot i of
- * host-buffer calls; 16 + 6 + 6 s + a is argument a of pipeline slot s).  *bytes = the workspace's size (0 if it does not exist
+ * variable-base kernels, 1: intermediate scalars / points of the ECDSA / ECDH / hash pipelines, 2: MSM workspace, 3: BIP340 challenges and the digests of the message-level calls, 16 + i: staging slot i of
+ * host-buffer calls; 16 + 6 + 6 s + a is argument a of pipeline slot s; the calls with seven buffers - the message-level signing
+ * calls - keep their fourth input in slot 24 and argument 6 of pipeline slot s in slot 25 + s).  *bytes = the workspace's size (0 if it does not exist
  * yet); if host_copy is not NULL the first min(cap, size) bytes are copied into it after the context's stream has drained.
  * For audits of secret hygiene: the tests read the workspaces back after secret-scalar calls and check that no result, prefix
  * product or staged secret is left (tests/test_gpu_ct_varbase.py). */
@@ -462,6 +463,48 @@ int ecgpu_hash_to_curve_batch(ecgpu_ctx* ctx, int curve, const uint8_t* msgs, si
  * staged messages and scalars are cleared before the call returns and the uniform bytes do not stay in the workspace. */
 int ecgpu_hash_to_scalar_batch(ecgpu_ctx* ctx, int curve, const uint8_t* msgs, size_t msg_stride, const uint32_t* msg_len,
                                const uint8_t* dst, size_t dst_len, uint8_t* out, size_t n, int mem);
+
+/* ---- from message bytes: digests, ECDSA and BIP340 ------------------------------------------------------------------
+ * Digest::digest for a batch: out[i] = SHA-256 (32 bytes) or SHA-384 (48 bytes) of message i, one message per lane.  The message
+ * arguments follow the rules above (ragged batches, msg_stride = 0, the refusal of a host-side msg_len[i] > msg_stride, a stride
+ * below 2^32).  A record that is 4-byte aligned has its whole blocks read by 32-bit words, any other one byte by byte
+ * (csrc/sha2.hpp, update_aligned): pad the stride to a multiple of 4 (host batches are staged from an aligned base) where the
+ * messages are long.  `out` is 4-byte aligned in device memory (a prehash call reads its rows as words); refused otherwise. */
+int ecgpu_digest_batch(ecgpu_ctx* ctx, int hash, const uint8_t* msgs, size_t msg_stride, const uint32_t* msg_len,
+                       uint8_t* out, size_t n, int mem);
+/* The message-level trait items of the reference: the digest kernel writes the curve's own digest (SHA-256 for secp256k1 and
+ * P-256, SHA-384 for P-384: DigestPrimitive::Digest, k256 | p256 | p384 src/ecdsa.rs) into the context's hash workspace, then
+ * the prehash call's pipeline runs on it, with that call's flags, outputs and chunking.  The digest is field-sized, so bits2field
+ * is the identity.  Any other digest stays with the prehash calls.  Messages and digests are public: nothing of them is cleared.
+ *
+ * Signer::sign (extra == NULL) / RandomizedSigner::sign_with_rng (extra given) of ecdsa::SigningKey (external ecdsa crate,
+ * src/signing.rs: try_sign hashes with C::Digest and enters sign_prehash): everything else as ecgpu_ecdsa_sign_prehash_batch -
+ * flags, sig_rs, recovery_id (optional), ok, the refusal of ECGPU_PUBLIC_SCALARS, the clearing of staged keys, additional data
+ * and nonces. */
+int ecgpu_ecdsa_sign_msg_batch(ecgpu_ctx* ctx, int curve, const uint8_t* secret_d, const uint8_t* msgs, size_t msg_stride,
+                               const uint32_t* msg_len, const uint8_t* extra, uint8_t* sig_rs, uint8_t* recovery_id,
+                               uint8_t* ok, size_t n, int mem, unsigned flags);
+/* Verifier::verify of ecdsa::VerifyingKey (external ecdsa crate, src/verifying.rs): as ecgpu_ecdsa_verify_batch on the digests. */
+int ecgpu_ecdsa_verify_msg_batch(ecgpu_ctx* ctx, int curve, const uint8_t* msgs, size_t msg_stride, const uint32_t* msg_len,
+                                 const uint8_t* sig_rs, const uint8_t* pubkeys_xy, uint8_t* ok, size_t n, int mem,
+                                 unsigned flags);
+/* VerifyingKey::recover_from_msg (external ecdsa crate, src/recovery.rs; k256/src/ecdsa.rs:259-336 exercises it): as
+ * ecgpu_ecdsa_recover_batch on the digests. */
+int ecgpu_ecdsa_recover_msg_batch(ecgpu_ctx* ctx, int curve, const uint8_t* msgs, size_t msg_stride, const uint32_t* msg_len,
+                                  const uint8_t* sig_rs, const uint8_t* recovery_id, uint8_t* pubkeys_xy, uint8_t* ok,
+                                  size_t n, int mem, unsigned flags);
+/* Signer::try_sign (aux_rand == NULL: the reference passes Default::default(), 32 zero bytes) / RandomizedSigner::try_sign_with_rng
+ * (aux_rand given) of k256's schnorr::SigningKey (k256/src/schnorr/signing.rs:214-218): sign_prehash_with_aux_rand over
+ * Sha256::new_with_prefix(msg), i.e. ecgpu_schnorr_sign_prehash_batch on SHA256(msg).  This is the reference's behaviour - BIP340
+ * over the 32-byte SHA-256 of the message - and NOT BIP340 with a variable-length message.  secp256k1 only: other curves give
+ * ECGPU_ERR_UNSUPPORTED. */
+int ecgpu_schnorr_sign_msg_batch(ecgpu_ctx* ctx, int curve, const uint8_t* secret_keys, const uint8_t* msgs, size_t msg_stride,
+                                 const uint32_t* msg_len, const uint8_t* aux_rand, uint8_t* sig_rs, uint8_t* pubkeys_x,
+                                 uint8_t* ok, size_t n, int mem);
+/* Verifier::verify of k256's schnorr::VerifyingKey (k256/src/schnorr/verifying.rs:94-98): ecgpu_schnorr_verify_prehash_batch on
+ * SHA256(msg), with the same remark: the reference's behaviour, not BIP340 with a variable-length message.  secp256k1 only. */
+int ecgpu_schnorr_verify_msg_batch(ecgpu_ctx* ctx, int curve, const uint8_t* pubkeys_x, const uint8_t* msgs, size_t msg_stride,
+                                   const uint32_t* msg_len, const uint8_t* sig_rs, uint8_t* ok, size_t n, int mem);
 
 /* ---- device groups: one call, several GPUs -------------------------------------------------------------------------------
  * The reference's bulk entry points are single calls over slices (LinearCombinationExt::lincomb_ext, k256 mul.rs:325-340; `&P * &k`

@@ -5,9 +5,9 @@
 // Every batched entry point is three parts: its argument checks, ONE list of its caller buffers (CallArg: pointer, direction,
 // bytes per element, secret or not) and one launch lambda, the only place that casts to the launcher's pointer types.
 // run_batch does the rest from the list.  Device memory: the pointers pass through.  Host memory: the buffers are staged in the
-// context's grow-only device slots - whole, the i-th input of the list in slot {0, 1, 4}[i] and the j-th output in {2, 3, 5}[j]
+// context's grow-only device slots - whole, the i-th input of the list in slot {0, 1, 4, 24}[i] and the j-th output in {2, 3, 5}[j]
 // (an absent optional buffer keeps its place in the count), or, for the calls that name a pass size and from PIPE_MIN elements
-// on, in chunks through the pipeline (host_pipe.hpp), list entry a of pipeline slot s in slot 6 + 6 s + a.  What the list marks
+// on, in chunks through the pipeline (host_pipe.hpp), list entry a of pipeline slot s in slot 6 + 6 s + a (a seventh entry: 25 + s).  What the list marks
 // secret is cleared from its slots (and from the pipeline's bounce buffers) before the call returns, whichever way it ends.
 #include <string.h>
 #include <condition_variable>
@@ -74,7 +74,7 @@ static constexpr CallArg arg_out(void* p, size_t unit, unsigned flags = 0) { ret
 
 // The slot rule (include/ecgpu.h, ecgpu_debug_workspace).  Staged whole, list entry k goes by its direction and by how many
 // entries of that direction precede it, present or absent; in the pipeline by its position alone (hostpipe::stage_index).
-static constexpr int WHOLE_IN_SLOT[3] = {0, 1, 4}, WHOLE_OUT_SLOT[3] = {2, 3, 5};
+static constexpr int WHOLE_IN_SLOT[4] = {0, 1, 4, ecgpu_ctx::STAGE_IN3}, WHOLE_OUT_SLOT[3] = {2, 3, 5};
 static constexpr int whole_slot(const CallArg* args, int k) {
   int before = 0;
   for (int i = 0; i < k; i++) before += args[i].is_out == args[k].is_out;
@@ -88,16 +88,20 @@ static_assert(whole_slot(sign, 3) == 2 && whole_slot(sign, 4) == 3 && whole_slot
 // ecgpu_ecdsa_recover_batch: z, sig, recid in; keys, ok out
 constexpr CallArg recover[5] = {arg_in(nullptr, 32), arg_in(nullptr, 64), arg_in(nullptr, 1), arg_out(nullptr, 64), arg_out(nullptr, 1)};
 static_assert(whole_slot(recover, 2) == 4 && whole_slot(recover, 3) == 2 && whole_slot(recover, 4) == 3, "recover: recovery ids in 4, keys in 2, ok in 3");
-static_assert(ecgpu_ctx::PIPE_STAGE0 == 6 && ecgpu_ctx::PIPE_MAXARGS == 6 && ecgpu_ctx::PIPE_NSLOT == 3, "6 whole-batch slots, then 3 pipeline slots of 6 arguments");
+static_assert(ecgpu_ctx::PIPE_STAGE0 == 6 && ecgpu_ctx::PIPE_ARGS0 == 6 && ecgpu_ctx::PIPE_NSLOT == 3, "6 whole-batch slots, then 3 pipeline slots of 6 arguments");
+// ecgpu_ecdsa_sign_msg_batch, seven buffers: d, msgs, msg_len, extra in; sig, recid, ok out
+constexpr CallArg sign_msg[7] = {arg_in(nullptr, 32), arg_in(nullptr, 1), arg_in(nullptr, 4), arg_in(nullptr, 32), arg_out(nullptr, 64), arg_out(nullptr, 1), arg_out(nullptr, 1)};
+static_assert(whole_slot(sign_msg, 3) == 24 && whole_slot(sign_msg, 4) == 2 && whole_slot(sign_msg, 6) == 5, "a fourth input: slot 24; the outputs keep 2, 3, 5");
+static_assert(hostpipe::stage_index(0, 6) == 25 && hostpipe::stage_index(2, 6) == 27, "a seventh argument of pipeline slot s: 25 + s");
 static_assert(hostpipe::stage_index(0, 0) == 6 && hostpipe::stage_index(1, 2) == 14 && hostpipe::stage_index(2, 5) == 23, "argument a of pipeline slot s: 6 + 6 s + a");
-static_assert(hostpipe::stage_index(ecgpu_ctx::PIPE_NSLOT - 1, ecgpu_ctx::PIPE_MAXARGS - 1) == ecgpu_ctx::NSTAGE - 1, "the last staging slot");
+static_assert(hostpipe::stage_index(ecgpu_ctx::PIPE_NSLOT - 1, ecgpu_ctx::PIPE_MAXARGS - 1) == ecgpu_ctx::NSTAGE - 1 && ecgpu_ctx::NSTAGE == 28, "the last staging slot");
 }  // namespace slot_rule_check
 
 // Staged copies of secret scalars do not outlive the call (the reference zeroizes its secrets): the guard clears the
 // bytes this call staged in its slots on EVERY exit path, the error returns included, and waits for the clearing.
 struct SecretWipe {
   ecgpu_ctx* c;
-  static constexpr int CAP = 3 * ecgpu_ctx::PIPE_NSLOT + 3;
+  static constexpr int CAP = 3 * ecgpu_ctx::PIPE_NSLOT + 3;      // no call marks more than three of its buffers secret
   int slot[CAP];
   size_t bytes[CAP];
   int cnt = 0;
@@ -170,7 +174,7 @@ static const ecgpu_curve_ops* ops_for(int curve) {
 
 extern "C" {
 
-const char* ecgpu_version(void) { return "ecgpu 0.7 (gfx950)"; }
+const char* ecgpu_version(void) { return "ecgpu 0.8 (gfx950)"; }
 
 size_t ecgpu_field_bytes(int curve) {
   switch (curve) {
@@ -740,16 +744,23 @@ int ecgpu_ecdh_batch(ecgpu_ctx* c, int curve, const uint8_t* secret_d, const uin
 // hash layer (h2c_hash.hpp): everything that starts from message bytes.  The messages of a call share one DST, which travels in the
 // kernels' argument block (XmdTail); msg_len is the optional per-message length.
 // ---------------------------------------------------------------------------------------------
+// the checks every call over messages makes (include/ecgpu.h, "Messages")
+static int msgs_enter(ecgpu_ctx* c, const uint8_t* msgs, size_t msg_stride, const uint32_t* msg_len, size_t n, int mem) {
+  if (msg_stride && !msgs) return ecgpu_set_err(c, ECGPU_ERR_ARG, "null argument");
+  if (msg_stride > 0xFFFFFFFFu) return ecgpu_set_err(c, ECGPU_ERR_ARG, "msg_stride %zu does not fit 32 bits", msg_stride);
+  if (msg_len && mem == ECGPU_MEM_HOST)
+    for (size_t i = 0; i < n; i++)
+      if (msg_len[i] > msg_stride) return ecgpu_set_err(c, ECGPU_ERR_ARG, "msg_len[%zu] = %u is above msg_stride = %zu", i, msg_len[i], msg_stride);
+  return 0;
+}
 // the checks every call over messages and a DST makes; fills `tail` for out_len uniform bytes per message
 static int xmd_enter(ecgpu_ctx* c, const uint8_t* msgs, size_t msg_stride, const uint32_t* msg_len, const uint8_t* dst, size_t dst_len, size_t out_len,
                      size_t n, int mem, ecgpu::h2c::XmdTail& tail) {
   if (dst_len == 0) return ecgpu_set_err(c, ECGPU_ERR_ARG, "expand_message_xmd: the DST is empty");
   if (!dst || (msg_stride && !msgs)) return ecgpu_set_err(c, ECGPU_ERR_ARG, "null argument");
   if (dst_len > 255) return ecgpu_set_err(c, ECGPU_ERR_ARG, "expand_message_xmd: DST of %zu bytes (above 255 the RFC rehashes it: not implemented)", dst_len);
-  if (msg_stride > 0xFFFFFFFFu) return ecgpu_set_err(c, ECGPU_ERR_ARG, "msg_stride %zu does not fit 32 bits", msg_stride);
-  if (msg_len && mem == ECGPU_MEM_HOST)
-    for (size_t i = 0; i < n; i++)
-      if (msg_len[i] > msg_stride) return ecgpu_set_err(c, ECGPU_ERR_ARG, "msg_len[%zu] = %u is above msg_stride = %zu", i, msg_len[i], msg_stride);
+  int rc = msgs_enter(c, msgs, msg_stride, msg_len, n, mem);
+  if (rc) return rc;
   ecgpu::h2c::xmd_tail_set(tail, dst, dst_len, out_len);
   return 0;
 }
@@ -840,6 +851,126 @@ int ecgpu_schnorr_verify_prehash_batch(ecgpu_ctx* c, int curve, const uint8_t* p
     if (r) return r;
     if ((r = ops->schnorr_challenge(c, (const uint32_t*)d[0], (const uint32_t*)d[1], (const uint32_t*)d[2], e, cnt))) return r;
     return ops->schnorr_verify(c, (const uint32_t*)d[0], (const uint32_t*)d[1], e, (uint8_t*)d[3], cnt);
+  });
+}
+
+// ---------------------------------------------------------------------------------------------
+// message level (include/ecgpu.h, "from message bytes"): the digest kernel writes the curve's own digest of every message into the
+// hash workspace, then the prehash form's launcher runs on it.  Messages and digests are public: nothing of them is wiped.
+// ---------------------------------------------------------------------------------------------
+int ecgpu_digest_batch(ecgpu_ctx* c, int hash, const uint8_t* msgs, size_t msg_stride, const uint32_t* msg_len, uint8_t* out, size_t n, int mem) {
+  if (!c || !out) return ecgpu_set_err(c, ECGPU_ERR_ARG, "null argument");
+  if (hash != ECGPU_SHA256 && hash != ECGPU_SHA384) return ecgpu_set_err(c, ECGPU_ERR_ARG, "unknown hash %d", hash);
+  if (mem == ECGPU_MEM_DEVICE && ((uintptr_t)out & 3u)) return ecgpu_set_err(c, ECGPU_ERR_ARG, "ecgpu_digest_batch: device-resident digests are 4-byte aligned");
+  int rc = msgs_enter(c, msgs, msg_stride, msg_len, n, mem);
+  if (rc) return rc;
+  if (n == 0) return ECGPU_OK;
+  std::lock_guard<std::mutex> lk(c->mu);
+  HIPCHK(c, hipSetDevice(c->device));
+  const CallArg args[] = {arg_in(msg_stride ? msgs : nullptr, msg_stride, ARG_OPTIONAL), arg_in(msg_len, 4, ARG_OPTIONAL), arg_out(out, hash == ECGPU_SHA384 ? 48 : 32)};
+  return run_batch(c, mem, n, args, (size_t)1 << 22, [&](void** d, size_t cnt) {
+    return ecgpuint_digest(c, hash, (const uint8_t*)d[0], msg_stride, (const uint32_t*)d[1], (uint32_t*)d[2], cnt);
+  });
+}
+// z = cnt digests of the curve's own hash in the hash workspace (the prehash launchers carve ecdsa_ws, never hash_ws)
+static int digest_to_ws(ecgpu_ctx* c, int curve, const void* msgs, size_t msg_stride, const void* msg_len, size_t cnt, uint32_t** z, uint32_t** more = nullptr) {
+  const size_t nb = ecgpu_field_bytes(curve);
+  int rc = ecgpu_carve(c, c->hash_ws, [&](WsCarver& ws) {
+    *z = ws.take<uint32_t>(cnt * nb);
+    if (more) *more = ws.take<uint32_t>(cnt * nb);
+  });
+  if (rc) return rc;
+  return ecgpuint_digest(c, curve_hash(curve), (const uint8_t*)msgs, msg_stride, (const uint32_t*)msg_len, *z, cnt);
+}
+int ecgpu_ecdsa_sign_msg_batch(ecgpu_ctx* c, int curve, const uint8_t* secret_d, const uint8_t* msgs, size_t msg_stride, const uint32_t* msg_len,
+                               const uint8_t* extra, uint8_t* sig_rs, uint8_t* recovery_id, uint8_t* ok, size_t n, int mem, unsigned flags) {
+  if (!c || !secret_d || !sig_rs || !ok) return ecgpu_set_err(c, ECGPU_ERR_ARG, "null argument");
+  if (flags & ECGPU_PUBLIC_SCALARS)
+    return ecgpu_set_err(c, ECGPU_ERR_ARG, "ecgpu_ecdsa_sign_msg_batch: ECGPU_PUBLIC_SCALARS is refused (a nonce derived from the key is never public)");
+  int rc = msgs_enter(c, msgs, msg_stride, msg_len, n, mem);
+  if (rc) return rc;
+  if (n == 0) return ECGPU_OK;
+  ENTER(c, curve);
+  const CallArg args[] = {arg_in(secret_d, nb, ARG_SECRET), arg_in(msg_stride ? msgs : nullptr, msg_stride, ARG_OPTIONAL), arg_in(msg_len, 4, ARG_OPTIONAL),
+                          arg_in(extra, nb, ARG_SECRET | ARG_OPTIONAL), arg_out(sig_rs, 2 * nb), arg_out(recovery_id, 1, ARG_OPTIONAL), arg_out(ok, 1)};
+  const unsigned fb_flags = (flags & ECGPU_EXACT_REFERENCE) ? (unsigned)ECGPU_EXACT_REFERENCE : (unsigned)ECGPU_SECRET_SCALARS;
+  return run_batch(c, mem, n, args, ops->pass_units(c, 0, 1, fb_flags), [&](void** d, size_t cnt) {
+    uint32_t* z;
+    int r = digest_to_ws(c, curve, d[1], msg_stride, d[2], cnt, &z);
+    if (r) return r;
+    return ops->ecdsa_sign_prehash(c, (const uint32_t*)d[0], z, (const uint32_t*)d[3], (uint32_t*)d[4], (uint8_t*)d[5], (uint8_t*)d[6], cnt, flags);
+  });
+}
+int ecgpu_ecdsa_verify_msg_batch(ecgpu_ctx* c, int curve, const uint8_t* msgs, size_t msg_stride, const uint32_t* msg_len, const uint8_t* sig_rs,
+                                 const uint8_t* pubkeys_xy, uint8_t* ok, size_t n, int mem, unsigned flags) {
+  if (!c || !sig_rs || !pubkeys_xy || !ok) return ecgpu_set_err(c, ECGPU_ERR_ARG, "null argument");
+  int rc = msgs_enter(c, msgs, msg_stride, msg_len, n, mem);
+  if (rc) return rc;
+  if (n == 0) return ECGPU_OK;
+  ENTER(c, curve);
+  const CallArg args[] = {arg_in(msg_stride ? msgs : nullptr, msg_stride, ARG_OPTIONAL), arg_in(msg_len, 4, ARG_OPTIONAL), arg_in(sig_rs, 2 * nb),
+                          arg_in(pubkeys_xy, 2 * nb), arg_out(ok, 1)};
+  return run_batch(c, mem, n, args, ops->pass_units(c, 1, 1, 0), [&](void** d, size_t cnt) {
+    uint32_t* z;
+    int r = digest_to_ws(c, curve, d[0], msg_stride, d[1], cnt, &z);
+    if (r) return r;
+    return ops->ecdsa_verify(c, z, (const uint32_t*)d[2], (const uint32_t*)d[3], (uint8_t*)d[4], cnt, flags);
+  });
+}
+int ecgpu_ecdsa_recover_msg_batch(ecgpu_ctx* c, int curve, const uint8_t* msgs, size_t msg_stride, const uint32_t* msg_len, const uint8_t* sig_rs,
+                                  const uint8_t* recovery_id, uint8_t* pubkeys_xy, uint8_t* ok, size_t n, int mem, unsigned flags) {
+  if (!c || !sig_rs || !recovery_id || !pubkeys_xy || !ok) return ecgpu_set_err(c, ECGPU_ERR_ARG, "null argument");
+  int rc = msgs_enter(c, msgs, msg_stride, msg_len, n, mem);
+  if (rc) return rc;
+  if (n == 0) return ECGPU_OK;
+  ENTER(c, curve);
+  const CallArg args[] = {arg_in(msg_stride ? msgs : nullptr, msg_stride, ARG_OPTIONAL), arg_in(msg_len, 4, ARG_OPTIONAL), arg_in(sig_rs, 2 * nb),
+                          arg_in(recovery_id, 1), arg_out(pubkeys_xy, 2 * nb), arg_out(ok, 1)};
+  return run_batch(c, mem, n, args, ops->pass_units(c, 1, 1, 0), [&](void** d, size_t cnt) {
+    uint32_t* z;
+    int r = digest_to_ws(c, curve, d[0], msg_stride, d[1], cnt, &z);
+    if (r) return r;
+    return ops->ecdsa_recover(c, z, (const uint32_t*)d[2], (const uint8_t*)d[3], (uint32_t*)d[4], (uint8_t*)d[5], cnt, flags);
+  });
+}
+// aux_rand == NULL is the reference's Default::default(), 32 zero bytes per key: the hash workspace holds them behind the digests
+int ecgpu_schnorr_sign_msg_batch(ecgpu_ctx* c, int curve, const uint8_t* secret_keys, const uint8_t* msgs, size_t msg_stride, const uint32_t* msg_len,
+                                 const uint8_t* aux_rand, uint8_t* sig_rs, uint8_t* pubkeys_x, uint8_t* ok, size_t n, int mem) {
+  if (!c || !secret_keys || !sig_rs || !ok) return ecgpu_set_err(c, ECGPU_ERR_ARG, "null argument");
+  if (ecgpu_field_bytes(curve) && curve != ECGPU_K256)
+    return ecgpu_set_err(c, ECGPU_ERR_UNSUPPORTED, "ecgpu_schnorr_sign_msg_batch: BIP340 is defined over secp256k1 only");
+  int rc = msgs_enter(c, msgs, msg_stride, msg_len, n, mem);
+  if (rc) return rc;
+  if (n == 0) return ECGPU_OK;
+  ENTER(c, curve);
+  const CallArg args[] = {arg_in(secret_keys, nb, ARG_SECRET), arg_in(msg_stride ? msgs : nullptr, msg_stride, ARG_OPTIONAL), arg_in(msg_len, 4, ARG_OPTIONAL),
+                          arg_in(aux_rand, 32, ARG_SECRET | ARG_OPTIONAL), arg_out(sig_rs, 2 * nb), arg_out(pubkeys_x, nb, ARG_OPTIONAL), arg_out(ok, 1)};
+  return run_batch(c, mem, n, args, ops->pass_units(c, 0, 1, ECGPU_SECRET_SCALARS), [&](void** d, size_t cnt) {
+    uint32_t *m, *zero_aux = nullptr;
+    int r = digest_to_ws(c, curve, d[1], msg_stride, d[2], cnt, &m, d[3] ? nullptr : &zero_aux);
+    if (r) return r;
+    if (zero_aux) HIPCHK(c, hipMemsetAsync(zero_aux, 0, cnt * 32, c->stream));
+    return ops->schnorr_sign_prehash(c, (const uint32_t*)d[0], m, d[3] ? (const uint32_t*)d[3] : zero_aux, (uint32_t*)d[4], (uint32_t*)d[5], (uint8_t*)d[6], cnt);
+  });
+}
+int ecgpu_schnorr_verify_msg_batch(ecgpu_ctx* c, int curve, const uint8_t* pubkeys_x, const uint8_t* msgs, size_t msg_stride, const uint32_t* msg_len,
+                                   const uint8_t* sig_rs, uint8_t* ok, size_t n, int mem) {
+  if (!c || !pubkeys_x || !sig_rs || !ok) return ecgpu_set_err(c, ECGPU_ERR_ARG, "null argument");
+  if (ecgpu_field_bytes(curve) && curve != ECGPU_K256)
+    return ecgpu_set_err(c, ECGPU_ERR_UNSUPPORTED, "ecgpu_schnorr_verify_msg_batch: BIP340 is defined over secp256k1 only");
+  int rc = msgs_enter(c, msgs, msg_stride, msg_len, n, mem);
+  if (rc) return rc;
+  if (n == 0) return ECGPU_OK;
+  ENTER(c, curve);
+  const CallArg args[] = {arg_in(pubkeys_x, nb), arg_in(msg_stride ? msgs : nullptr, msg_stride, ARG_OPTIONAL), arg_in(msg_len, 4, ARG_OPTIONAL),
+                          arg_in(sig_rs, 2 * nb), arg_out(ok, 1)};
+  return run_batch(c, mem, n, args, ops->pass_units(c, 1, 1, 0), [&](void** d, size_t cnt) {
+    // the digests and the challenges live through schnorr_verify, which carves ecdsa_ws: both come from ONE carve of hash_ws
+    uint32_t *m, *e;
+    int r = digest_to_ws(c, curve, d[1], msg_stride, d[2], cnt, &m, &e);
+    if (r) return r;
+    if ((r = ops->schnorr_challenge(c, (const uint32_t*)d[0], (const uint32_t*)d[3], m, e, cnt))) return r;
+    return ops->schnorr_verify(c, (const uint32_t*)d[0], (const uint32_t*)d[3], e, (uint8_t*)d[4], cnt);
   });
 }
 

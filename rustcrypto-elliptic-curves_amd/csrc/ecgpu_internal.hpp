@@ -40,9 +40,12 @@ struct ecgpu_ctx {
   std::mutex mu;
   std::mutex err_mu;                          // guards err[] (ecgpu_set_err / ecgpu_last_error_copy)
   int64_t opt[ECGPU_OPT_COUNT_] = {0, 26, 0, 0, 1, 0, 4, 0, 0};      // ecgpu_option defaults
-  // grow-only device staging buffers for ECGPU_MEM_HOST calls: 6 for whole-batch staging, then PIPE_NSLOT pipeline slots x PIPE_MAXARGS arguments
-  static constexpr int PIPE_NSLOT = 3, PIPE_MAXARGS = 6, PIPE_STAGE0 = 6;
-  static constexpr int NSTAGE = PIPE_STAGE0 + PIPE_NSLOT * PIPE_MAXARGS;
+  // grow-only device staging buffers for ECGPU_MEM_HOST calls: 6 for whole-batch staging, then PIPE_NSLOT pipeline slots x PIPE_ARGS0 arguments.
+  // The message-level signing calls have a seventh buffer (four inputs): its slots follow behind, so that every older slot keeps its
+  // number - STAGE_IN3 for a whole batch, then one per pipeline slot (hostpipe::stage_index).
+  static constexpr int PIPE_NSLOT = 3, PIPE_ARGS0 = 6, PIPE_MAXARGS = 7, PIPE_STAGE0 = 6;
+  static constexpr int STAGE_IN3 = PIPE_STAGE0 + PIPE_NSLOT * PIPE_ARGS0, PIPE_STAGE1 = STAGE_IN3 + 1;
+  static constexpr int NSTAGE = PIPE_STAGE1 + PIPE_NSLOT * (PIPE_MAXARGS - PIPE_ARGS0);
   DevBuf stage[NSTAGE];
   // chunked host-buffer pipeline (host_pipe.hpp): download and upload streams, per-slot events (inputs arrived / kernels done /
   // outputs read), and the page-locked bounce buffers pageable caller memory is copied through ([0] uploads, [1] downloads)
@@ -70,8 +73,8 @@ struct ecgpu_ctx {
   // intermediates of the pipelines: carved by the curve's entry launcher (curve_ops.hpp), or by the API layer (ecgpu.hip) where
   // the launchers it strings together carve nothing
   DevBuf ecdsa_ws;
-  // BIP340 challenges of ecgpu_schnorr_verify_prehash_batch, carved by the API layer: they live through schnorr_verify, which
-  // carves ecdsa_ws
+  // BIP340 challenges of ecgpu_schnorr_verify_prehash_batch and the digests of the message-level calls (with the challenges or the
+  // zero aux_rand behind them: one carve), carved by the API layer: they live through the prehash launchers, which carve ecdsa_ws
   DevBuf hash_ws;
 };
 
@@ -202,6 +205,8 @@ struct ecgpu_curve_ops {
 };
 // expand_message_xmd to raw bytes on `hash` (ecgpu_hash), curve-independent (h2c_hash.hip): out = n x tail.out_len bytes
 int ecgpuint_xmd(ecgpu_ctx* c, int hash, const uint8_t* msgs, size_t msg_stride, const uint32_t* msg_len, const ecgpu::h2c::XmdTail& tail, uint8_t* out, size_t n);
+// plain digests on `hash` (h2c_hash.hip): out = n rows of 32 / 48 bytes, 4-byte aligned
+int ecgpuint_digest(ecgpu_ctx* c, int hash, const uint8_t* msgs, size_t msg_stride, const uint32_t* msg_len, uint32_t* out, size_t n);
 // Pippenger MSM, one translation unit per curve (msm_*.hip); `mul` is the curve's batch scalar multiplication (affine in / out
 // on device memory), used for small sums
 typedef int (*ecgpu_msm_mul_fn)(ecgpu_ctx* c, const uint32_t* scalars, const uint32_t* points, int pt_fmt, uint32_t* out_xy, size_t n);

@@ -145,6 +145,24 @@ ECGPU_HD void bip340_challenge(u32* e, const u32* r, const u32* px, const u32* m
   for (int i = 0; i < 8; i++) e[i] = bswap32(h[i]);
 }
 
+// The plain digest of one message (Digest::digest; what Signer::sign and Verifier::verify of the ecdsa crate and k256's BIP340 keys
+// run before their prehash forms) as DIGEST_BYTES / 4 words as they lie in memory: out is 4-byte aligned, so that a prehash
+// kernel reads the row as const uint32_t*.  Whole blocks of a 4-byte aligned record come in by words (sha2::update_aligned).
+template <class H>
+ECGPU_HD void digest_words(u32* out, const uint8_t* msg, u32 msg_len) {
+  using W = typename H::W;
+  sha2::State<H> s;
+  sha2::init(s);
+  sha2::update_aligned(s, msg, msg_len);
+  W d[8];
+  sha2::finish(s, d);
+#pragma unroll
+  for (int j = 0; j < H::DIGEST_BYTES / (int)sizeof(W); j++) {
+    if constexpr (sizeof(W) == 4) out[j] = bswap32(d[j]);
+    else { out[2 * j] = bswap32((u32)(d[j] >> 32)); out[2 * j + 1] = bswap32((u32)d[j]); }
+  }
+}
+
 #if defined(__HIPCC__)
 // message i: msg_stride bytes at msgs + i * msg_stride, of which msg_len[i] count (all of them without msg_len).  A length
 // above the stride is the caller's error (refused for host buffers); it is clamped so that no read leaves the record.
@@ -169,6 +187,13 @@ __global__ void __launch_bounds__(256) xmd_kernel(const uint8_t* msgs, size_t ms
         if (base + k < out_len) o[base + k] = (uint8_t)sha2::digest_byte<H>(d, k);
     });
   }
+}
+// plain digests: out[i] = the DIGEST_BYTES of message i (rows 4-byte aligned)
+template <class H>
+__global__ void __launch_bounds__(256) digest_kernel(const uint8_t* msgs, size_t msg_stride, const u32* msg_len, u32* out, size_t n) {
+  const size_t T = (size_t)gridDim.x * blockDim.x;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += T)
+    digest_words<H>(out + i * (H::DIGEST_BYTES / 4), msgs + i * msg_stride, message_length(msg_len, i, msg_stride));
 }
 // expand_message_xmd fused with FromOkm: u[i] = count field elements in the layout h2c::map_kernel reads
 template <class C, int COUNT>

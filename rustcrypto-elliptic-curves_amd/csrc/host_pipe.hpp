@@ -145,7 +145,10 @@ static inline int ensure_resources(ecgpu_ctx* c, bool need_bounce_up, bool need_
 struct Piece { int arg; size_t off, len; };     // byte range of one argument's chunk
 
 // stage slot of argument a in pipeline slot s (ecgpu.hip: stage_reserve)
-static constexpr int stage_index(int slot, int a) { return ecgpu_ctx::PIPE_STAGE0 + slot * ecgpu_ctx::PIPE_MAXARGS + a; }
+static constexpr int stage_index(int slot, int a) {
+  return a < ecgpu_ctx::PIPE_ARGS0 ? ecgpu_ctx::PIPE_STAGE0 + slot * ecgpu_ctx::PIPE_ARGS0 + a
+                                   : ecgpu_ctx::PIPE_STAGE1 + slot * (ecgpu_ctx::PIPE_MAXARGS - ecgpu_ctx::PIPE_ARGS0) + (a - ecgpu_ctx::PIPE_ARGS0);
+}
 
 template <class Reserve, class Launch>
 static int run(ecgpu_ctx* c, const Arg* args, int nargs, const std::vector<size_t>& sizes, bool secret, Reserve reserve, Launch launch) {

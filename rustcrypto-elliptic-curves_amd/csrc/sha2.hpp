@@ -8,7 +8,8 @@
 // Rounds run in groups of sixteen; the round constants are read with the (wave-uniform) group counter.
 //
 // Constant time in the message: no branch and no address depends on a message byte.  Lengths are public: they steer the
-// loops, the padding and the addresses of the byte loads.
+// loops, the padding and the addresses of the byte loads.  So is the address of a message: update_aligned reads the whole blocks
+// of a 4-byte aligned message by words (the digest of whole messages, h2c_hash.hpp digest_words; profiles/message_signing.txt).
 //
 // rotr on 32 bits is one v_alignbit_b32, on 64 bits two of them on the register halves (profiles/h2c_hash_entry_points.txt).
 // Everything is ECGPU_HD: tests/hosttwin compiles the same text for the host.
@@ -185,6 +186,36 @@ ECGPU_HD void update(State<H>& s, const uint8_t* p, u32 len) {
       fill = 0;
     }
   }
+}
+// one naturally aligned 32-bit load, as the big-endian word its four bytes spell
+ECGPU_HD u32 load_be32(const uint8_t* p) {
+  u32 v;
+  __builtin_memcpy(&v, __builtin_assume_aligned(p, 4), 4);
+  return bswap32(v);
+}
+// `update` for whole messages: where the state stands at a block boundary and p is 4-byte aligned, every whole block comes in by
+// sixteen (SHA-384: thirty-two) aligned 32-bit loads and a byte swap instead of one load and sixteen compares per byte; the
+// partial last block, and everything where either condition fails, goes through `update` as it stands.  Which way a message goes
+// depends on its address and on lengths alone (public); the word loads lie inside [p, p + len) and round no address.
+template <class H>
+ECGPU_HD void update_aligned(State<H>& s, const uint8_t* p, u32 len) {
+  using W = typename H::W;
+  constexpr u32 BB = H::BLOCK_BYTES;
+  const bool words = (s.total & (BB - 1)) == 0 && ((uintptr_t)p & 3u) == 0;
+  const u32 whole = words ? len / BB : 0u;
+#pragma unroll 1
+  for (u32 b = 0; b < whole; b++) {
+    const uint8_t* q = p + b * BB;
+#pragma unroll
+    for (u32 j = 0; j < 16; j++) {
+      if constexpr (sizeof(W) == 4) s.w[j] = load_be32(q + 4 * j);
+      else s.w[j] = (W)load_be32(q + 8 * j) << 32 | load_be32(q + 8 * j + 4);
+    }
+    compress<H>(s.h, s.w);
+  }
+  if (whole) clear_block(s);
+  s.total += whole * BB;
+  update(s, p + whole * BB, len - whole * BB);
 }
 // one byte whose position does not end the block (the caller knows the fill: a counter behind a digest)
 template <class H>

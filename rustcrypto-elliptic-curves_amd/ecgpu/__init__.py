@@ -157,6 +157,12 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
     lib.ecgpu_rfc6979_nonce_batch.argtypes = [vp, i, u8p, u8p, u8p, u8p, sz, i]
     lib.ecgpu_ecdsa_sign_prehash_batch.argtypes = [vp, i, u8p, u8p, u8p, u8p, u8p, u8p, sz, i, ctypes.c_uint]
     lib.ecgpu_schnorr_sign_prehash_batch.argtypes = [vp, i, u8p, u8p, u8p, u8p, u8p, u8p, sz, i]
+    lib.ecgpu_digest_batch.argtypes = [vp, i, u8p, sz, u8p, u8p, sz, i]
+    lib.ecgpu_ecdsa_sign_msg_batch.argtypes = [vp, i, u8p, u8p, sz, u8p, u8p, u8p, u8p, u8p, sz, i, ctypes.c_uint]
+    lib.ecgpu_ecdsa_verify_msg_batch.argtypes = [vp, i, u8p, sz, u8p, u8p, u8p, u8p, sz, i, ctypes.c_uint]
+    lib.ecgpu_ecdsa_recover_msg_batch.argtypes = [vp, i, u8p, sz, u8p, u8p, u8p, u8p, u8p, sz, i, ctypes.c_uint]
+    lib.ecgpu_schnorr_sign_msg_batch.argtypes = [vp, i, u8p, u8p, sz, u8p, u8p, u8p, u8p, u8p, sz, i]
+    lib.ecgpu_schnorr_verify_msg_batch.argtypes = [vp, i, u8p, u8p, sz, u8p, u8p, u8p, sz, i]
     lib.ecgpu_synth_scalars.argtypes = [vp, i, ctypes.c_uint64, ctypes.c_uint64, u8p, sz]
     lib.ecgpu_synth_points.argtypes = [vp, i, ctypes.c_uint64, ctypes.c_uint64, u8p, sz]
     for name in ("ecgpu_create", "ecgpu_set_stream", "ecgpu_synchronize", "ecgpu_timer_start", "ecgpu_timer_stop",
@@ -172,7 +178,8 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
                  "ecgpu_group_synchronize", "ecgpu_shard_range", "ecgpu_group_mul_batch", "ecgpu_group_lincomb_batch", "ecgpu_group_lincomb_sharded",
                  "ecgpu_group_msm", "ecgpu_group_msm_sharded", "ecgpu_schnorr_verify_prehash_batch", "ecgpu_expand_message_xmd_batch",
                  "ecgpu_field_from_okm_batch", "ecgpu_hash_to_curve_batch", "ecgpu_hash_to_scalar_batch", "ecgpu_rfc6979_nonce_batch",
-                 "ecgpu_ecdsa_sign_prehash_batch", "ecgpu_schnorr_sign_prehash_batch"):
+                 "ecgpu_ecdsa_sign_prehash_batch", "ecgpu_schnorr_sign_prehash_batch", "ecgpu_digest_batch", "ecgpu_ecdsa_sign_msg_batch",
+                 "ecgpu_ecdsa_verify_msg_batch", "ecgpu_ecdsa_recover_msg_batch", "ecgpu_schnorr_sign_msg_batch", "ecgpu_schnorr_verify_msg_batch"):
         getattr(lib, name).restype = ctypes.c_int
     if path is None:
         _lib = lib
@@ -194,6 +201,8 @@ EXPORTED_SYMBOLS = (
     "ecgpu_group_msm", "ecgpu_group_msm_sharded",
     "ecgpu_schnorr_verify_prehash_batch", "ecgpu_expand_message_xmd_batch", "ecgpu_field_from_okm_batch", "ecgpu_hash_to_curve_batch",
     "ecgpu_hash_to_scalar_batch", "ecgpu_rfc6979_nonce_batch", "ecgpu_ecdsa_sign_prehash_batch", "ecgpu_schnorr_sign_prehash_batch",
+    "ecgpu_digest_batch", "ecgpu_ecdsa_sign_msg_batch", "ecgpu_ecdsa_verify_msg_batch", "ecgpu_ecdsa_recover_msg_batch",
+    "ecgpu_schnorr_sign_msg_batch", "ecgpu_schnorr_verify_msg_batch",
 )
 
 
@@ -274,7 +283,7 @@ class Context:
 
     def debug_workspace(self, which: int) -> bytes:
         """contents of one of the context's device workspaces (ecgpu_debug_workspace): 0 table workspace, 1 ECDSA / ECDH
-        intermediates, 2 MSM, 16 + i staging slot i.  b"" if it does not exist yet."""
+        intermediates, 2 MSM, 3 BIP340 challenges and message digests, 16 + i staging slot i (0 .. 27).  b"" if it does not exist yet."""
         b = ctypes.c_size_t()
         self.check(self.lib.ecgpu_debug_workspace(self.handle, which, None, 0, ctypes.byref(b)))
         if not b.value:
@@ -335,6 +344,29 @@ def pack_messages(msgs: Sequence[bytes], stride: Optional[int] = None):
     for k, m in enumerate(msgs):
         rec[k, :len(m)] = np.frombuffer(m, dtype=np.uint8)
     return rec, lens, stride
+
+
+def pack_messages_aligned(msgs: Sequence[bytes]):
+    """pack_messages with the stride padded to a multiple of 16: the records of a host batch are staged from an aligned base, so
+    every one of them is 16-byte aligned and its whole blocks are read by words (csrc/sha2.hpp, update_aligned)"""
+    longest = max((len(m) for m in msgs), default=0)
+    return pack_messages(msgs, (longest + 15) // 16 * 16)
+
+
+DIGEST_BYTES = {0: 32, 1: 48}       # by ecgpu_hash
+
+
+def digest(ctx: "Context", hash_id: int, msgs: Sequence[bytes]) -> np.ndarray:
+    """SHA-256 / SHA-384 of every message on the device -> (n, 32 | 48) digests (ecgpu_digest_batch)"""
+    rec, lens, stride = pack_messages_aligned(msgs)
+    out = _host_out(len(msgs), DIGEST_BYTES.get(hash_id, 48))
+    ctx.check(ctx.lib.ecgpu_digest_batch(ctx.handle, hash_id, _ptr(rec)[0] if stride else None, stride, _ptr(lens)[0], _ptr(out)[0], len(msgs), HOST))
+    return out
+
+
+def digest_device(ctx: "Context", hash_id: int, d_msgs, msg_stride: int, d_msg_len, d_out, n: int):
+    """the same over device buffers (d_msg_len may be None: every message is msg_stride bytes; d_out 4-byte aligned)"""
+    ctx.check(ctx.lib.ecgpu_digest_batch(ctx.handle, hash_id, _ptr(d_msgs)[0], msg_stride, _ptr(d_msg_len)[0], _ptr(d_out)[0], n, DEVICE))
 
 
 def expand_message_xmd(ctx: "Context", hash_id: int, msgs: Sequence[bytes], dst: bytes, out_bytes: int) -> np.ndarray:
@@ -744,6 +776,83 @@ class Curve:
     def schnorr_sign_prehash_device(self, d_secret, d_prehash, d_aux, d_sig_rs, d_pubkeys_x, d_ok, n: int):
         self.ctx.check(self.ctx.lib.ecgpu_schnorr_sign_prehash_batch(self.ctx.handle, self.id, _ptr(d_secret)[0], _ptr(d_prehash)[0], _ptr(d_aux)[0],
                                                                      _ptr(d_sig_rs)[0], _ptr(d_pubkeys_x)[0], _ptr(d_ok)[0], n, DEVICE))
+
+    # --- from message bytes: the curve's own digest runs on the device, then the prehash pipeline -------------
+    def digest(self, msgs: Sequence[bytes]) -> np.ndarray:
+        """the curve's own digest of every message (SHA-256; P-384: SHA-384) -> (n, NB)"""
+        return digest(self.ctx, CURVE_HASH[self.id], msgs)
+
+    def ecdsa_sign_msg(self, secret_d, msgs: Sequence[bytes], extra=None, flags: Optional[int] = None):
+        """Signer::sign (extra=None) / RandomizedSigner::sign_with_rng (extra given) for a batch -> (sig_rs, recovery_id, ok)"""
+        d = _as_host(secret_d, self.nb)
+        x = None if extra is None else _as_host(extra, self.nb)
+        if len(d) != len(msgs) or (x is not None and len(x) != len(d)):
+            raise ValueError("key, message and additional-data batches differ in length")
+        rec, lens, stride = pack_messages_aligned(msgs)
+        sig, rid, ok = _host_out(len(d), 2 * self.nb), np.zeros(len(d), dtype=np.uint8), np.zeros(len(d), dtype=np.uint8)
+        fl = self.default_ecdsa_flags() if flags is None else flags
+        self.ctx.check(self.ctx.lib.ecgpu_ecdsa_sign_msg_batch(self.ctx.handle, self.id, _ptr(d)[0], _ptr(rec)[0] if stride else None, stride, _ptr(lens)[0],
+                                                               _ptr(x)[0], _ptr(sig)[0], _ptr(rid)[0], _ptr(ok)[0], len(d), HOST, fl))
+        return sig, rid, ok
+
+    def ecdsa_sign_msg_device(self, d_secret, d_msgs, msg_stride: int, d_msg_len, d_extra, d_sig_rs, d_recid, d_ok, n: int, flags: Optional[int] = None):
+        fl = self.default_ecdsa_flags() if flags is None else flags
+        self.ctx.check(self.ctx.lib.ecgpu_ecdsa_sign_msg_batch(self.ctx.handle, self.id, _ptr(d_secret)[0], _ptr(d_msgs)[0], msg_stride, _ptr(d_msg_len)[0],
+                                                               _ptr(d_extra)[0], _ptr(d_sig_rs)[0], _ptr(d_recid)[0], _ptr(d_ok)[0], n, DEVICE, fl))
+
+    def ecdsa_verify_msg(self, msgs: Sequence[bytes], sig_rs, pubkeys_xy, flags: Optional[int] = None) -> np.ndarray:
+        """Verifier::verify for a batch -> ok"""
+        sg, q = _as_host(sig_rs, 2 * self.nb), _as_host(pubkeys_xy, 2 * self.nb)
+        if not (len(msgs) == len(sg) == len(q)):
+            raise ValueError("message, signature and public-key batches differ in length")
+        rec, lens, stride = pack_messages_aligned(msgs)
+        ok = np.zeros(len(sg), dtype=np.uint8)
+        fl = self.default_ecdsa_flags() if flags is None else flags
+        self.ctx.check(self.ctx.lib.ecgpu_ecdsa_verify_msg_batch(self.ctx.handle, self.id, _ptr(rec)[0] if stride else None, stride, _ptr(lens)[0], _ptr(sg)[0],
+                                                                 _ptr(q)[0], _ptr(ok)[0], len(sg), HOST, fl))
+        return ok
+
+    def ecdsa_verify_msg_device(self, d_msgs, msg_stride: int, d_msg_len, d_sig_rs, d_pubkeys_xy, d_ok, n: int, flags: Optional[int] = None):
+        fl = self.default_ecdsa_flags() if flags is None else flags
+        self.ctx.check(self.ctx.lib.ecgpu_ecdsa_verify_msg_batch(self.ctx.handle, self.id, _ptr(d_msgs)[0], msg_stride, _ptr(d_msg_len)[0], _ptr(d_sig_rs)[0],
+                                                                 _ptr(d_pubkeys_xy)[0], _ptr(d_ok)[0], n, DEVICE, fl))
+
+    def ecdsa_recover_msg(self, msgs: Sequence[bytes], sig_rs, recovery_id, flags: Optional[int] = None):
+        """VerifyingKey::recover_from_msg for a batch -> (pubkeys_xy, ok)"""
+        sg = _as_host(sig_rs, 2 * self.nb)
+        rid = np.ascontiguousarray(recovery_id, dtype=np.uint8).reshape(-1)
+        if not (len(msgs) == len(sg) == len(rid)):
+            raise ValueError("message, signature and recovery-id batches differ in length")
+        rec, lens, stride = pack_messages_aligned(msgs)
+        out, ok = _host_out(len(sg), 2 * self.nb), np.zeros(len(sg), dtype=np.uint8)
+        fl = self.default_ecdsa_flags() if flags is None else flags
+        self.ctx.check(self.ctx.lib.ecgpu_ecdsa_recover_msg_batch(self.ctx.handle, self.id, _ptr(rec)[0] if stride else None, stride, _ptr(lens)[0], _ptr(sg)[0],
+                                                                  _ptr(rid)[0], _ptr(out)[0], _ptr(ok)[0], len(sg), HOST, fl))
+        return out, ok
+
+    def schnorr_sign_msg(self, secret_keys, msgs: Sequence[bytes], aux_rands=None):
+        """BIP340 Signer::try_sign (aux_rands=None: 32 zero bytes) / try_sign_with_rng over SHA256(msg) for a batch (secp256k1)
+        -> (sig_rs, pubkeys_x, ok)"""
+        d = _as_host(secret_keys, self.nb)
+        a = None if aux_rands is None else _as_host(aux_rands, 32)
+        if len(d) != len(msgs) or (a is not None and len(a) != len(d)):
+            raise ValueError("key, message and aux_rand batches differ in length")
+        rec, lens, stride = pack_messages_aligned(msgs)
+        sig, px, ok = _host_out(len(d), 2 * self.nb), _host_out(len(d), self.nb), np.zeros(len(d), dtype=np.uint8)
+        self.ctx.check(self.ctx.lib.ecgpu_schnorr_sign_msg_batch(self.ctx.handle, self.id, _ptr(d)[0], _ptr(rec)[0] if stride else None, stride, _ptr(lens)[0],
+                                                                 _ptr(a)[0], _ptr(sig)[0], _ptr(px)[0], _ptr(ok)[0], len(d), HOST))
+        return sig, px, ok
+
+    def schnorr_verify_msg(self, pubkeys_x, msgs: Sequence[bytes], sig_rs) -> np.ndarray:
+        """BIP340 Verifier::verify over SHA256(msg) for a batch (secp256k1) -> ok"""
+        x, sg = _as_host(pubkeys_x, self.nb), _as_host(sig_rs, 2 * self.nb)
+        if not (len(x) == len(sg) == len(msgs)):
+            raise ValueError("key, message and signature batches differ in length")
+        rec, lens, stride = pack_messages_aligned(msgs)
+        ok = np.zeros(len(x), dtype=np.uint8)
+        self.ctx.check(self.ctx.lib.ecgpu_schnorr_verify_msg_batch(self.ctx.handle, self.id, _ptr(x)[0], _ptr(rec)[0] if stride else None, stride, _ptr(lens)[0],
+                                                                   _ptr(sg)[0], _ptr(ok)[0], len(x), HOST))
+        return ok
 
     # --- synthetic inputs (device buffers) ---------------------------------------------------------
     def synth_scalars_device(self, d_out, n: int, seed: int, first_index: int = 0):

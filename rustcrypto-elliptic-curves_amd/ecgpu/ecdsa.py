@@ -55,6 +55,44 @@ def sign_prehash(curve: Curve, secret_keys: Sequence[bytes], digests: Sequence[b
     return curve.ecdsa_sign_prehash(b"".join(secret_keys), z, None if extra is None else b"".join(extra), flags)
 
 
+def verify_der_batch_device(curve: Curve, pubkeys_xy: Sequence[bytes], messages: Sequence[bytes], der_sigs: Sequence[bytes],
+                            normalize_s: bool = False) -> np.ndarray:
+    """verify_der_batch with the messages hashed on the device (ecgpu_ecdsa_verify_msg_batch: Verifier::verify): DER decoding stays
+    on the host, the digests never exist there.  A signature that does not decode keeps a zero r || s, which never verifies."""
+    nb = curve.nb
+    n = len(der_sigs)
+    order = ORDER[curve.id]
+    sig = bytearray(n * 2 * nb)
+    decoded = np.zeros(n, dtype=np.uint8)
+    for i in range(n):
+        rs = decode_signature(der_sigs[i], nb)
+        if rs is None:
+            continue                       # Signature::from_der -> Err
+        r, s = rs
+        if normalize_s and s > order // 2 and s < order:
+            s = order - s
+        decoded[i] = 1
+        sig[2 * nb * i:2 * nb * (i + 1)] = r.to_bytes(nb, "big") + s.to_bytes(nb, "big")
+    ok = curve.ecdsa_verify_msg(list(messages), bytes(sig), b"".join(pubkeys_xy))
+    return ok & decoded
+
+
+def sign_msg(curve: Curve, secret_keys: Sequence[bytes], messages: Sequence[bytes], extra: Sequence[bytes] | None = None, flags=None):
+    """Signer::sign (extra=None) / RandomizedSigner::sign_with_rng for a batch of messages: the curve's own digest, the RFC 6979
+    nonces and the signatures all on the device (ecgpu_ecdsa_sign_msg_batch) -> (sig_rs, recovery_id, ok)"""
+    return curve.ecdsa_sign_msg(b"".join(secret_keys), list(messages), None if extra is None else b"".join(extra), flags)
+
+
+def verify_msg(curve: Curve, pubkeys_xy: Sequence[bytes], messages: Sequence[bytes], sigs_rs: Sequence[bytes], flags=None) -> np.ndarray:
+    """Verifier::verify for a batch of fixed-width r || s signatures (ecgpu_ecdsa_verify_msg_batch)"""
+    return curve.ecdsa_verify_msg(list(messages), b"".join(sigs_rs), b"".join(pubkeys_xy), flags)
+
+
+def recover_from_msg(curve: Curve, messages: Sequence[bytes], sigs_rs: Sequence[bytes], recovery_ids: Sequence[int], flags=None):
+    """VerifyingKey::recover_from_msg for a batch (ecgpu_ecdsa_recover_msg_batch) -> (pubkeys_xy, ok)"""
+    return curve.ecdsa_recover_msg(list(messages), b"".join(sigs_rs), np.array(list(recovery_ids), dtype=np.uint8), flags)
+
+
 ORDER = {
     K256: 0xFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFEBAAEDCE6AF48A03BBFD25E8CD0364141,
     P256: 0xFFFFFFFF00000000FFFFFFFFFFFFFFFFBCE6FAADA7179E84F3B9CAC2FC632551,

@@ -88,3 +88,23 @@ def sign_batch_device(curve: Curve, secret_keys: Sequence[bytes], prehashes: Seq
     if not ok.all():
         raise ValueError("signing failed for element %d (secret key out of range, or a zero nonce or s)" % int(np.argmin(ok)))
     return [bytes(r) for r in sig], [bytes(r) for r in px]
+
+
+def sign_msg_batch_device(curve: Curve, secret_keys: Sequence[bytes], messages: Sequence[bytes], aux_rands: Sequence[bytes] | None = None):
+    """Signer::try_sign (aux_rands=None: 32 zero bytes, signing.rs:214-218) / try_sign_with_rng for a batch of messages of any
+    length: SHA256(msg) on the device, then as sign_batch_device (ecgpu_schnorr_sign_msg_batch) -> (signatures, public keys x-only).
+    This is the reference's BIP340 over the digest of the message, not BIP340 with a variable-length message."""
+    if curve.id != K256:
+        raise ValueError("BIP340 is defined over secp256k1")
+    sig, px, ok = curve.schnorr_sign_msg(b"".join(secret_keys), list(messages), None if aux_rands is None else b"".join(aux_rands))
+    if not ok.all():
+        raise ValueError("signing failed for element %d (secret key out of range, or a zero nonce or s)" % int(np.argmin(ok)))
+    return [bytes(r) for r in sig], [bytes(r) for r in px]
+
+
+def verify_msg_batch_device(curve: Curve, pubkeys_x: Sequence[bytes], messages: Sequence[bytes], sigs: Sequence[bytes]) -> np.ndarray:
+    """Verifier::verify (verifying.rs:94-98) for a batch: verify_prehash over SHA256(msg), the digest computed on the device too
+    (ecgpu_schnorr_verify_msg_batch)."""
+    if curve.id != K256:
+        raise ValueError("BIP340 is defined over secp256k1")
+    return curve.schnorr_verify_msg(b"".join(pubkeys_x), list(messages), b"".join(sigs))

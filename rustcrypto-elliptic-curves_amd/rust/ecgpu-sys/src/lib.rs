@@ -150,6 +150,17 @@ extern "C" {
                                      mode: c_int, out_xy: *mut u8, out_inf: *mut u8, n: usize, mem: c_int) -> c_int;
     pub fn ecgpu_hash_to_scalar_batch(ctx: *mut ecgpu_ctx, curve: c_int, msgs: *const u8, msg_stride: usize, msg_len: *const u32, dst: *const u8, dst_len: usize,
                                       out: *mut u8, n: usize, mem: c_int) -> c_int;
+    pub fn ecgpu_digest_batch(ctx: *mut ecgpu_ctx, hash: c_int, msgs: *const u8, msg_stride: usize, msg_len: *const u32, out: *mut u8, n: usize, mem: c_int) -> c_int;
+    pub fn ecgpu_ecdsa_sign_msg_batch(ctx: *mut ecgpu_ctx, curve: c_int, secret_d: *const u8, msgs: *const u8, msg_stride: usize, msg_len: *const u32, extra: *const u8,
+                                      sig_rs: *mut u8, recovery_id: *mut u8, ok: *mut u8, n: usize, mem: c_int, flags: c_uint) -> c_int;
+    pub fn ecgpu_ecdsa_verify_msg_batch(ctx: *mut ecgpu_ctx, curve: c_int, msgs: *const u8, msg_stride: usize, msg_len: *const u32, sig_rs: *const u8,
+                                        pubkeys_xy: *const u8, ok: *mut u8, n: usize, mem: c_int, flags: c_uint) -> c_int;
+    pub fn ecgpu_ecdsa_recover_msg_batch(ctx: *mut ecgpu_ctx, curve: c_int, msgs: *const u8, msg_stride: usize, msg_len: *const u32, sig_rs: *const u8,
+                                         recovery_id: *const u8, pubkeys_xy: *mut u8, ok: *mut u8, n: usize, mem: c_int, flags: c_uint) -> c_int;
+    pub fn ecgpu_schnorr_sign_msg_batch(ctx: *mut ecgpu_ctx, curve: c_int, secret_keys: *const u8, msgs: *const u8, msg_stride: usize, msg_len: *const u32,
+                                        aux_rand: *const u8, sig_rs: *mut u8, pubkeys_x: *mut u8, ok: *mut u8, n: usize, mem: c_int) -> c_int;
+    pub fn ecgpu_schnorr_verify_msg_batch(ctx: *mut ecgpu_ctx, curve: c_int, pubkeys_x: *const u8, msgs: *const u8, msg_stride: usize, msg_len: *const u32,
+                                          sig_rs: *const u8, ok: *mut u8, n: usize, mem: c_int) -> c_int;
     pub fn ecgpu_group_create(group: *mut *mut ecgpu_group, devices: *const c_int, n_devices: c_int, flags: c_uint) -> c_int;
     pub fn ecgpu_group_destroy(group: *mut ecgpu_group);
     pub fn ecgpu_group_size(group: *const ecgpu_group) -> c_int;
@@ -462,6 +473,83 @@ impl Context {
         let mut rec = vec![0u8; stride * msgs.len()];
         for (i, m) in msgs.iter().enumerate() { rec[i * stride..i * stride + m.len()].copy_from_slice(m); }
         (rec, msgs.iter().map(|m| m.len() as u32).collect(), stride)
+    }
+    /// pack_messages with the stride padded to a multiple of 16: staged records are aligned, so their whole blocks are read by words
+    fn pack_messages_aligned(msgs: &[&[u8]]) -> (Vec<u8>, Vec<u32>, usize) {
+        let stride = (msgs.iter().map(|m| m.len()).max().unwrap_or(0) + 15) / 16 * 16;
+        let mut rec = vec![0u8; stride * msgs.len()];
+        for (i, m) in msgs.iter().enumerate() { rec[i * stride..i * stride + m.len()].copy_from_slice(m); }
+        (rec, msgs.iter().map(|m| m.len() as u32).collect(), stride)
+    }
+    /// Digest::digest for a batch (hash: ECGPU_SHA256 | ECGPU_SHA384) -> 32 | 48 bytes per message
+    pub fn digest(&self, hash: c_int, msgs: &[&[u8]]) -> Result<Vec<u8>, Error> {
+        Self::arg(hash == ECGPU_SHA256 || hash == ECGPU_SHA384)?;
+        let (rec, lens, stride) = Self::pack_messages_aligned(msgs);
+        let mut out = vec![0u8; (if hash == ECGPU_SHA384 { 48 } else { 32 }) * msgs.len()];
+        self.check(unsafe { ecgpu_digest_batch(self.0, hash, rec.as_ptr(), stride, lens.as_ptr(), out.as_mut_ptr(), msgs.len(), ECGPU_MEM_HOST) })?;
+        Ok(out)
+    }
+    /// `Signer::sign` (`extra = None`) / `RandomizedSigner::sign_with_rng` (`extra`: field-sized random bytes per signature) for a
+    /// batch of messages, hashed on the device with the curve's own digest -> (r || s, recovery ids, ok flags)
+    pub fn ecdsa_sign_msg(&self, curve: c_int, secret_d: &[u8], msgs: &[&[u8]], extra: Option<&[u8]>, flags: c_uint) -> Result<(Vec<u8>, Vec<u8>, Vec<u8>), Error> {
+        let nb = Self::field_bytes(curve);
+        Self::arg(nb != 0 && secret_d.len() == nb * msgs.len() && extra.map_or(true, |e| e.len() == secret_d.len()))?;
+        let n = msgs.len();
+        let (rec, lens, stride) = Self::pack_messages_aligned(msgs);
+        let (mut sig, mut rid, mut ok) = (vec![0u8; 2 * nb * n], vec![0u8; n], vec![0u8; n]);
+        self.check(unsafe {
+            ecgpu_ecdsa_sign_msg_batch(self.0, curve, secret_d.as_ptr(), rec.as_ptr(), stride, lens.as_ptr(), extra.map_or(core::ptr::null(), |e| e.as_ptr()),
+                                       sig.as_mut_ptr(), rid.as_mut_ptr(), ok.as_mut_ptr(), n, ECGPU_MEM_HOST, flags)
+        })?;
+        Ok((sig, rid, ok))
+    }
+    /// `Verifier::verify` for a batch of messages -> ok flags
+    pub fn ecdsa_verify_msg(&self, curve: c_int, msgs: &[&[u8]], sig_rs: &[u8], pubkeys_xy: &[u8], flags: c_uint) -> Result<Vec<u8>, Error> {
+        let nb = Self::field_bytes(curve);
+        Self::arg(nb != 0 && sig_rs.len() == 2 * nb * msgs.len() && pubkeys_xy.len() == sig_rs.len())?;
+        let (rec, lens, stride) = Self::pack_messages_aligned(msgs);
+        let mut ok = vec![0u8; msgs.len()];
+        self.check(unsafe {
+            ecgpu_ecdsa_verify_msg_batch(self.0, curve, rec.as_ptr(), stride, lens.as_ptr(), sig_rs.as_ptr(), pubkeys_xy.as_ptr(), ok.as_mut_ptr(), msgs.len(), ECGPU_MEM_HOST,
+                                         flags)
+        })?;
+        Ok(ok)
+    }
+    /// `VerifyingKey::recover_from_msg` for a batch -> (x || y, ok flags)
+    pub fn ecdsa_recover_msg(&self, curve: c_int, msgs: &[&[u8]], sig_rs: &[u8], recovery_id: &[u8], flags: c_uint) -> Result<(Vec<u8>, Vec<u8>), Error> {
+        let nb = Self::field_bytes(curve);
+        Self::arg(nb != 0 && sig_rs.len() == 2 * nb * msgs.len() && recovery_id.len() == msgs.len())?;
+        let n = msgs.len();
+        let (rec, lens, stride) = Self::pack_messages_aligned(msgs);
+        let (mut xy, mut ok) = (vec![0u8; 2 * nb * n], vec![0u8; n]);
+        self.check(unsafe {
+            ecgpu_ecdsa_recover_msg_batch(self.0, curve, rec.as_ptr(), stride, lens.as_ptr(), sig_rs.as_ptr(), recovery_id.as_ptr(), xy.as_mut_ptr(), ok.as_mut_ptr(), n,
+                                          ECGPU_MEM_HOST, flags)
+        })?;
+        Ok((xy, ok))
+    }
+    /// BIP340 `Signer::try_sign` (`aux_rands = None`: 32 zero bytes, the reference's `Default::default()`) / `try_sign_with_rng` over
+    /// SHA256(msg) for a batch (secp256k1) -> (r || s, x-only public keys, ok flags)
+    pub fn schnorr_sign_msg(&self, secret_keys: &[u8], msgs: &[&[u8]], aux_rands: Option<&[u8]>) -> Result<(Vec<u8>, Vec<u8>, Vec<u8>), Error> {
+        Self::arg(secret_keys.len() == 32 * msgs.len() && aux_rands.map_or(true, |a| a.len() == secret_keys.len()))?;
+        let n = msgs.len();
+        let (rec, lens, stride) = Self::pack_messages_aligned(msgs);
+        let (mut sig, mut px, mut ok) = (vec![0u8; 64 * n], vec![0u8; 32 * n], vec![0u8; n]);
+        self.check(unsafe {
+            ecgpu_schnorr_sign_msg_batch(self.0, ECGPU_K256, secret_keys.as_ptr(), rec.as_ptr(), stride, lens.as_ptr(), aux_rands.map_or(core::ptr::null(), |a| a.as_ptr()),
+                                         sig.as_mut_ptr(), px.as_mut_ptr(), ok.as_mut_ptr(), n, ECGPU_MEM_HOST)
+        })?;
+        Ok((sig, px, ok))
+    }
+    /// BIP340 `Verifier::verify` over SHA256(msg) for a batch (secp256k1) -> ok flags
+    pub fn schnorr_verify_msg(&self, pubkeys_x: &[u8], msgs: &[&[u8]], sig_rs: &[u8]) -> Result<Vec<u8>, Error> {
+        Self::arg(pubkeys_x.len() == 32 * msgs.len() && sig_rs.len() == 2 * pubkeys_x.len())?;
+        let (rec, lens, stride) = Self::pack_messages_aligned(msgs);
+        let mut ok = vec![0u8; msgs.len()];
+        self.check(unsafe {
+            ecgpu_schnorr_verify_msg_batch(self.0, ECGPU_K256, pubkeys_x.as_ptr(), rec.as_ptr(), stride, lens.as_ptr(), sig_rs.as_ptr(), ok.as_mut_ptr(), msgs.len(), ECGPU_MEM_HOST)
+        })?;
+        Ok(ok)
     }
     /// ExpandMsgXmd::expand_message for a batch (hash: ECGPU_SHA256 | ECGPU_SHA384) -> out_bytes uniform bytes per message
     pub fn expand_message_xmd(&self, hash: c_int, msgs: &[&[u8]], dst: &[u8], out_bytes: usize) -> Result<Vec<u8>, Error> {

@@ -168,3 +168,40 @@ pub fn schnorr_sign_prehash_batch(gpu: &Context, secret_keys: &[[u8; 32]], preha
     Ok(sig.chunks_exact(64).zip(px.chunks_exact(32)).zip(ok.iter())
         .map(|((s, p), k)| if *k != 0 { Some((s.try_into().unwrap(), p.try_into().unwrap())) } else { None }).collect())
 }
+
+/// `Signer<Signature>::sign` of `ecdsa::SigningKey<Secp256k1>` for many (key, message) pairs: SHA-256 of each message runs on the
+/// device, then everything of `ecdsa_sign_prehash_batch`.  `added`: the additional data of `RandomizedSigner::sign_with_rng`.
+pub fn ecdsa_sign_batch(gpu: &Context, keys: &[Scalar], msgs: &[&[u8]], added: Option<&[[u8; 32]]>) -> Result<Vec<Option<([u8; 64], u8)>>, Error> {
+    assert!(keys.len() == msgs.len() && added.map_or(true, |a| a.len() == keys.len()));
+    let ad = added.map(|a| a.concat());
+    let (sig, rec, ok) = gpu.ecdsa_sign_msg(ECGPU_K256, &put_scalars(keys.iter()), msgs, ad.as_deref(), ecgpu_sys::ECGPU_ECDSA_LOW_S)?;
+    Ok(sig.chunks_exact(64).zip(rec.iter().zip(ok.iter())).map(|(s, (r, k))| if *k != 0 { Some((s.try_into().unwrap(), *r)) } else { None }).collect())
+}
+/// `Verifier<Signature>::verify` of `ecdsa::VerifyingKey<Secp256k1>` for many (message, r || s, x || y) triples (low-s rule as
+/// ecdsa.rs:198-207).
+pub fn ecdsa_verify_batch(gpu: &Context, msgs: &[&[u8]], sigs: &[[u8; 64]], pubkeys_xy: &[[u8; 64]]) -> Result<Vec<bool>, Error> {
+    assert!(msgs.len() == sigs.len() && sigs.len() == pubkeys_xy.len());
+    let ok = gpu.ecdsa_verify_msg(ECGPU_K256, msgs, &sigs.concat(), &pubkeys_xy.concat(), ecgpu_sys::ECGPU_ECDSA_LOW_S)?;
+    Ok(ok.into_iter().map(|f| f != 0).collect())
+}
+/// `VerifyingKey::recover_from_msg` (exercised by ecdsa.rs:259-336) -> x || y of each key, None where the reference returns Err.
+pub fn ecdsa_recover_from_msg_batch(gpu: &Context, msgs: &[&[u8]], sigs: &[[u8; 64]], recovery_ids: &[u8]) -> Result<Vec<Option<[u8; 64]>>, Error> {
+    assert!(msgs.len() == sigs.len() && sigs.len() == recovery_ids.len());
+    let (xy, ok) = gpu.ecdsa_recover_msg(ECGPU_K256, msgs, &sigs.concat(), recovery_ids, ecgpu_sys::ECGPU_ECDSA_LOW_S)?;
+    Ok(xy.chunks_exact(64).zip(ok.iter()).map(|(p, k)| if *k != 0 { Some(p.try_into().unwrap()) } else { None }).collect())
+}
+/// `Signer<Signature>::try_sign` of `schnorr::SigningKey` (schnorr/signing.rs:214-218; `aux_rands = None`: the reference's
+/// `Default::default()`) / `RandomizedSigner::try_sign_with_rng`: BIP340 over SHA256(msg), the digest computed on the device too.
+pub fn schnorr_sign_batch(gpu: &Context, secret_keys: &[[u8; 32]], msgs: &[&[u8]], aux_rands: Option<&[[u8; 32]]>) -> Result<Vec<Option<([u8; 64], [u8; 32])>>, Error> {
+    assert!(secret_keys.len() == msgs.len() && aux_rands.map_or(true, |a| a.len() == msgs.len()));
+    let aux = aux_rands.map(|a| a.concat());
+    let (sig, px, ok) = gpu.schnorr_sign_msg(&secret_keys.concat(), msgs, aux.as_deref())?;
+    Ok(sig.chunks_exact(64).zip(px.chunks_exact(32)).zip(ok.iter())
+        .map(|((s, p), k)| if *k != 0 { Some((s.try_into().unwrap(), p.try_into().unwrap())) } else { None }).collect())
+}
+/// `Verifier<Signature>::verify` of `schnorr::VerifyingKey` (schnorr/verifying.rs:94-98): `verify_prehash` over SHA256(msg).
+pub fn schnorr_verify_batch(gpu: &Context, pubkeys_x: &[[u8; 32]], msgs: &[&[u8]], sigs: &[[u8; 64]]) -> Result<Vec<bool>, Error> {
+    assert!(pubkeys_x.len() == msgs.len() && msgs.len() == sigs.len());
+    let ok = gpu.schnorr_verify_msg(&pubkeys_x.concat(), msgs, &sigs.concat())?;
+    Ok(ok.into_iter().map(|f| f != 0).collect())
+}

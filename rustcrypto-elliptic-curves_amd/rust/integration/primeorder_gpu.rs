@@ -124,3 +124,22 @@ fn ecdsa_sign_prehash_with<C: GpuCurve>(gpu: &Context, keys: &[Scalar<C>], diges
     let (sig, rec, ok) = gpu.ecdsa_sign_prehash(C::ECGPU_ID, &put_scalars::<C>(keys.iter()), &flat(digests), ad.as_deref(), 0)?;
     Ok(sig.chunks_exact(2 * nb::<C>()).zip(rec.iter().zip(ok.iter())).map(|(s, (r, k))| if *k != 0 { Some((s.to_vec(), *r)) } else { None }).collect())
 }
+
+/// `Signer<Signature<C>>::sign` of `ecdsa::SigningKey<C>` for many (key, message) pairs: the curve's own digest (SHA-256 for P-256,
+/// SHA-384 for P-384) runs on the device, then everything of `ecdsa_sign_prehash_batch`.  `added`: the additional data of
+/// `RandomizedSigner::sign_with_rng`.
+pub fn ecdsa_sign_batch<C: GpuCurve>(gpu: &Context, keys: &[Scalar<C>], msgs: &[&[u8]], added: Option<&[FieldBytes<C>]>) -> Result<Vec<Option<(Vec<u8>, u8)>>, Error> {
+    assert!(keys.len() == msgs.len() && added.map_or(true, |a| a.len() == keys.len()));
+    let ad = added.map(|v| { let mut o = Vec::with_capacity(nb::<C>() * v.len()); for b in v { o.extend_from_slice(b.as_ref()); } o });
+    let (sig, rec, ok) = gpu.ecdsa_sign_msg(C::ECGPU_ID, &put_scalars::<C>(keys.iter()), msgs, ad.as_deref(), 0)?;
+    Ok(sig.chunks_exact(2 * nb::<C>()).zip(rec.iter().zip(ok.iter())).map(|(s, (r, k))| if *k != 0 { Some((s.to_vec(), *r)) } else { None }).collect())
+}
+/// `Verifier<Signature<C>>::verify` of `ecdsa::VerifyingKey<C>` for many (message, r || s, x || y) triples, all flat big-endian bytes.
+pub fn ecdsa_verify_batch<C: GpuCurve>(gpu: &Context, msgs: &[&[u8]], sigs_rs: &[u8], pubkeys_xy: &[u8]) -> Result<Vec<bool>, Error> {
+    Ok(gpu.ecdsa_verify_msg(C::ECGPU_ID, msgs, sigs_rs, pubkeys_xy, 0)?.into_iter().map(|f| f != 0).collect())
+}
+/// `VerifyingKey::<C>::recover_from_msg` -> x || y of each key, None where the reference returns Err.
+pub fn ecdsa_recover_from_msg_batch<C: GpuCurve>(gpu: &Context, msgs: &[&[u8]], sigs_rs: &[u8], recovery_ids: &[u8]) -> Result<Vec<Option<Vec<u8>>>, Error> {
+    let (xy, ok) = gpu.ecdsa_recover_msg(C::ECGPU_ID, msgs, sigs_rs, recovery_ids, 0)?;
+    Ok(xy.chunks_exact(2 * nb::<C>()).zip(ok.iter()).map(|(p, k)| if *k != 0 { Some(p.to_vec()) } else { None }).collect())
+}
