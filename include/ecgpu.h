@@ -506,6 +506,52 @@ int ecgpu_schnorr_sign_msg_batch(ecgpu_ctx* ctx, int curve, const uint8_t* secre
 int ecgpu_schnorr_verify_msg_batch(ecgpu_ctx* ctx, int curve, const uint8_t* pubkeys_x, const uint8_t* msgs, size_t msg_stride,
                                    const uint32_t* msg_len, const uint8_t* sig_rs, uint8_t* ok, size_t n, int mem);
 
+/* ---- BIP340 batch verification ("Batch Verification" of the BIP) ---------------------------------------------------------
+ * The n signatures of a call are checked with ONE equation,
+ *     sum_i a_i R_i + sum_i (a_i e_i) P_i - (sum_i a_i s_i) G = O,      R_i = lift_x(r_i), P_i = lift_x(pubkey_i),
+ * a multi-scalar multiplication over 2n + 1 terms on the kernels of ecgpu_msm, with two square roots and two scalar products
+ * per signature in front of it.  The coefficients are a_i = the first 16 bytes, big-endian, of
+ * SHA256(tag || tag || seed32 || be64(i)), tag = SHA256("ecgpu/BIP340/batch-coefficient"), 0 replaced by 1, i the element's index in
+ * the caller's batch.
+ *
+ * SOUNDNESS RESTS ON THE SEED.  seed32 is 32 bytes of HOST memory whatever `mem` says.  It must be unpredictable to whoever produced
+ * the signatures, and it must not be used again on data an adversary chose after seeing a result for it: someone who knows the
+ * coefficients makes invalid signatures whose errors cancel in the sum.  seed32 = NULL lets the library draw 32 bytes with
+ * getrandom(2) for this call (ECGPU_ERR_RUNTIME if that fails); pass a seed only to reproduce a run.
+ *
+ * ok[i] is the byte ecgpu_schnorr_verify_prehash_batch writes for the element, with ONE exception: an equation over elements of
+ * which one is invalid holds with probability 2^-128 over the seed - for the other coefficients fixed, one value of a_i satisfies it,
+ * and every value has that probability but 1, which stands in for 0 too: at most 2^-127 - and its ok bytes are then 1.  An element that does not decode (r
+ * outside [1, p) or not an x-coordinate, s outside [1, n), a key without a curve point) is invalid for the per-signature verifier
+ * as well; it gets ok[i] = 0 and is left out of the equation, never causing the fallback below.
+ * *all_valid (HOST memory, may be NULL) is set to 1 iff every ok[i] is - or, without ok, would be - 1.  n = 0 gives 1.
+ *
+ * Where the equation holds, the call is done.  Where it does not, at least one signature is invalid and the per-signature pipeline of
+ * ecgpu_schnorr_verify_batch runs over the same elements to say which: A FAILING BATCH COSTS THE EQUATION PLUS THE PER-SIGNATURE CALL.
+ *   ECGPU_BATCH_VERDICT_ONLY     no fallback.  ok may be NULL; if given it holds the decode flags where the equation held and zeros
+ *                                for a whole equation that failed.
+ *   ECGPU_BATCH_EQUATION_ALWAYS  the equation at every n >= 1.  By default a batch below 2^18 signatures runs the per-signature
+ *                                pipeline and fills all_valid from ok: under the small-sum limit of ecgpu_msm (2n + 1 below 5 * 2^14
+ *                                terms) the MSM is itself one multiplication per term, and measured on an MI355X the equation equals
+ *                                the per-signature call at 2^16 and wins from 2^18 on (1.36 x; 1.77 x at 2^20, 1.85 x at 2^22).
+ *                                (A call without ok takes the equation at every n as well; a batch that is routed to the
+ *                                per-signature pipeline gets its exact ok bytes with ECGPU_BATCH_VERDICT_ONLY too.)
+ * A device-resident batch is one equation (below 2^31 signatures).  A host-resident batch of 2^21 elements and more is cut into the
+ * chunks of the host pipeline; every chunk is an equation of its own over its elements' coefficients, and all_valid is the AND.
+ * The calls SYNCHRONISE the context's stream - the verdict of every equation is read on the host -, so the chunks of such a host
+ * batch do not overlap their copies with the next chunk's kernels.
+ * Arguments otherwise as in ecgpu_schnorr_verify_batch (challenges), ecgpu_schnorr_verify_prehash_batch (32-byte digests) and
+ * ecgpu_schnorr_verify_msg_batch (message records).  secp256k1 only: other curves give ECGPU_ERR_UNSUPPORTED.  Nothing here is
+ * secret; the terms of the last equation stay in workspace 1 (ecgpu_debug_workspace: the 2n + 1 scalars first). */
+enum { ECGPU_BATCH_VERDICT_ONLY = 16u, ECGPU_BATCH_EQUATION_ALWAYS = 32u };
+int ecgpu_schnorr_batch_verify(ecgpu_ctx* ctx, int curve, const uint8_t* pubkeys_x, const uint8_t* sig_rs, const uint8_t* challenges,
+                               const uint8_t* seed32, uint8_t* ok, int* all_valid, size_t n, int mem, unsigned flags);
+int ecgpu_schnorr_batch_verify_prehash(ecgpu_ctx* ctx, int curve, const uint8_t* pubkeys_x, const uint8_t* sig_rs, const uint8_t* prehash,
+                                       const uint8_t* seed32, uint8_t* ok, int* all_valid, size_t n, int mem, unsigned flags);
+int ecgpu_schnorr_batch_verify_msg(ecgpu_ctx* ctx, int curve, const uint8_t* pubkeys_x, const uint8_t* msgs, size_t msg_stride,
+                                   const uint32_t* msg_len, const uint8_t* sig_rs, const uint8_t* seed32, uint8_t* ok, int* all_valid,
+                                   size_t n, int mem, unsigned flags);
+
 /* ---- device groups: one call, several GPUs -------------------------------------------------------------------------------
  * The reference's bulk entry points are single calls over slices (LinearCombinationExt::lincomb_ext, k256 mul.rs:325-340; `&P * &k`
  * element by element, mul.rs:442-481), so the split over devices lives on this side of the boundary:

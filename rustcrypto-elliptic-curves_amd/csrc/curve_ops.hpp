@@ -7,6 +7,7 @@
 #include "ecdh_kernels.hpp"
 #include "sec1_kernels.hpp"
 #include "schnorr_kernels.hpp"
+#include "schnorr_batch_kernels.hpp"
 #include "signing_kernels.hpp"
 #include "h2c_kernels.hpp"
 #include "h2c_hash.hpp"
@@ -366,16 +367,17 @@ struct CurveOps {
     u32 *u1, *u2, *pt, *a, *b;
     uint8_t *a_inf, *b_inf;
   };
+  static void verify_layout(WsCarver& ws, size_t n, bool with_pt, VerifyWs& w) {
+    w.u1 = ws.take<u32>(n * C::NB);
+    w.u2 = ws.take<u32>(n * C::NB);
+    w.pt = with_pt ? ws.take<u32>(n * 2 * C::NB) : nullptr;
+    w.a = ws.take<u32>(n * 2 * C::NB);
+    w.b = ws.take<u32>(n * 2 * C::NB);
+    w.a_inf = ws.take<uint8_t>(n);
+    w.b_inf = ws.take<uint8_t>(n);
+  }
   static int verify_ws(ecgpu_ctx* c, size_t n, bool with_pt, VerifyWs& w) {
-    return ecgpu_carve(c, c->ecdsa_ws, [&](WsCarver& ws) {
-      w.u1 = ws.take<u32>(n * C::NB);
-      w.u2 = ws.take<u32>(n * C::NB);
-      w.pt = with_pt ? ws.take<u32>(n * 2 * C::NB) : nullptr;
-      w.a = ws.take<u32>(n * 2 * C::NB);
-      w.b = ws.take<u32>(n * 2 * C::NB);
-      w.a_inf = ws.take<uint8_t>(n);
-      w.b_inf = ws.take<uint8_t>(n);
-    });
+    return ecgpu_carve(c, c->ecdsa_ws, [&](WsCarver& ws) { verify_layout(ws, n, with_pt, w); });
   }
   // a = u1 G, b = u2 Q (after the prep kernel's launch check).  One term each: lincomb cannot reach lincomb_straus, which carves ecdsa_ws.
   static int verify_products(ecgpu_ctx* c, const VerifyWs& w, const u32* q, size_t n) {
@@ -413,7 +415,20 @@ struct CurveOps {
     HIPCHK(c, hipGetLastError());
     return 0;
   }
-  // BIP340 verification (schnorr_kernels.hpp), secp256k1 only
+  // BIP340 verification (schnorr_kernels.hpp), secp256k1 only.  The body runs on the caller's workspace layout (with_pt).
+  static int schnorr_verify_body(ecgpu_ctx* c, const VerifyWs& w, const u32* px, const u32* sig, const u32* e, uint8_t* ok, size_t n) {
+    if constexpr (C::ID != 0) {
+      return ecgpu_set_err(c, ECGPU_ERR_UNSUPPORTED, "ecgpu_schnorr_verify_batch: BIP340 is defined over secp256k1 only");
+    } else {
+      hipLaunchKernelGGL((schnorr::verify_prep_kernel<0>), dim3(ecgpu_grid_for(c, n, 8)), dim3(256), 0, c->stream, px, sig, e, w.pt, w.u1, w.u2, ok, n);
+      int rc = verify_products(c, w, w.pt, n);
+      if (rc) return rc;
+      hipLaunchKernelGGL((schnorr::verify_check_kernel<16>), dim3(ecgpu_grid_for(c, (n + 15) / 16, 8)), dim3(256), 0, c->stream, (const u32*)w.a,
+                         (const uint8_t*)w.a_inf, (const u32*)w.b, (const uint8_t*)w.b_inf, sig, ok, n);
+      HIPCHK(c, hipGetLastError());
+      return 0;
+    }
+  }
   static int schnorr_verify(ecgpu_ctx* c, const u32* px, const u32* sig, const u32* e, uint8_t* ok, size_t n) {
     if constexpr (C::ID != 0) {
       return ecgpu_set_err(c, ECGPU_ERR_UNSUPPORTED, "ecgpu_schnorr_verify_batch: BIP340 is defined over secp256k1 only");
@@ -421,12 +436,63 @@ struct CurveOps {
       VerifyWs w;
       int rc = verify_ws(c, n, true, w);
       if (rc) return rc;
-      hipLaunchKernelGGL((schnorr::verify_prep_kernel<0>), dim3(ecgpu_grid_for(c, n, 8)), dim3(256), 0, c->stream, px, sig, e, w.pt, w.u1, w.u2, ok, n);
-      if ((rc = verify_products(c, w, w.pt, n))) return rc;
-      hipLaunchKernelGGL((schnorr::verify_check_kernel<16>), dim3(ecgpu_grid_for(c, (n + 15) / 16, 8)), dim3(256), 0, c->stream, (const u32*)w.a,
-                         (const uint8_t*)w.a_inf, (const u32*)w.b, (const uint8_t*)w.b_inf, sig, ok, n);
+      return schnorr_verify_body(c, w, px, sig, e, ok, n);
+    }
+  }
+  // BIP340 batch verification (schnorr_batch_kernels.hpp): one equation over the n signatures of this call, elements first_index ..
+  // of the caller's batch.  prep (terms 0 .. 2n - 1, dec, the partial sums of a_i s_i) -> finish (term 2n) -> msm over 2n + 1 terms
+  // -> the point and the count of left-out elements come to the host: the equation holds iff Z = 0.  Then ok = dec; otherwise
+  // the per-signature body runs over the whole call, unless ECGPU_BATCH_VERDICT_ONLY asks for zeros.  ok may be NULL with that flag.
+  // ONE carve of ecdsa_ws: the equation's buffers and the fallback's VerifyWs lie over the same bytes, the fallback starting when the
+  // equation's buffers are dead.  msm carves msm_ws only - its small-sum path too: msm_run's carve (msm_kernels.hpp) names msm_ws, and its
+  // `mul` is lincomb on ONE term (ops_*.hip), which reaches lincomb_fast / the reference kernels (tab_ws), never lincomb_straus.
+  static int schnorr_batch_verify(ecgpu_ctx* c, const u32* px, const u32* sig, const u32* e, uint8_t* ok, size_t n, uint64_t first_index,
+                                  const uint8_t* seed32, unsigned flags, int* verdict) {
+    if constexpr (C::ID != 0) {
+      return ecgpu_set_err(c, ECGPU_ERR_UNSUPPORTED, "ecgpu_schnorr_batch_verify: BIP340 is defined over secp256k1 only");
+    } else {
+      namespace sb = schnorr_batch;
+      if (n >= ((size_t)1 << 31)) return ecgpu_set_err(c, ECGPU_ERR_ARG, "ecgpu_schnorr_batch_verify: at most 2^31 - 1 signatures per equation");
+      const bool verdict_only = (flags & ECGPU_BATCH_VERDICT_ONLY) != 0;
+      const size_t terms = 2 * n + 1;
+      const unsigned grid = ecgpu_grid_for(c, n, 8);
+      u32 *sc, *pts, *partial, *res;
+      uint8_t* dec;
+      VerifyWs w;
+      int rc = ecgpu_carve(c, c->ecdsa_ws, [&](WsCarver& ws) {
+        sc = ws.take<u32>(terms * C::NB);                    // first: ecgpu_debug_workspace 1 shows the scalars at offset 0
+        pts = ws.take<u32>(terms * 2 * C::NB);
+        partial = ws.take<u32>((size_t)grid * sb::PARTIAL_WORDS * sizeof(u32));
+        res = ws.take<u32>(32 * sizeof(u32));                // 24 words of X : Y : Z, then the count of left-out elements
+        dec = ws.take<uint8_t>(n);
+        const size_t equation_bytes = ws.total;
+        ws.total = 0;
+        if (!verdict_only) verify_layout(ws, n, true, w);
+        if (ws.total < equation_bytes) ws.total = equation_bytes;
+      });
+      if (rc) return rc;
+      if (ok) dec = ok;                                      // ok = dec where the equation holds; overwritten where it does not
+      sb::Seed seed;
+      for (int i = 0; i < 8; i++)
+        seed.w[i] = (u32)seed32[4 * i] << 24 | (u32)seed32[4 * i + 1] << 16 | (u32)seed32[4 * i + 2] << 8 | (u32)seed32[4 * i + 3];
+      hipLaunchKernelGGL((sb::prep_kernel<0>), dim3(grid), dim3(256), 0, c->stream, px, sig, e, seed, (u64)first_index, sc, pts, dec, partial, n);
+      hipLaunchKernelGGL((sb::finish_kernel<0>), dim3(1), dim3(64), 0, c->stream, (const u32*)partial, (int)grid, sc + 2 * n * C::NW,
+                         pts + 2 * n * 2 * C::NW, res + 24);
       HIPCHK(c, hipGetLastError());
-      return 0;
+      if ((rc = msm(c, sc, pts, FMT_AFFINE, terms, res, FMT_PROJECTIVE))) return rc;
+      u32 host_res[25];
+      HIPCHK(c, hipMemcpyAsync(host_res, res, sizeof(host_res), hipMemcpyDeviceToHost, c->stream));
+      HIPCHK(c, hipStreamSynchronize(c->stream));
+      u32 z = 0;
+      for (int i = 16; i < 24; i++) z |= host_res[i];
+      const bool holds = z == 0;
+      *verdict = (holds && host_res[24] == 0) ? 1 : 0;
+      if (holds) return 0;
+      if (verdict_only) {
+        if (ok) HIPCHK(c, hipMemsetAsync(ok, 0, n, c->stream));
+        return 0;
+      }
+      return schnorr_verify_body(c, w, px, sig, e, ok, n);
     }
   }
   // ECDH (ecdh_kernels.hpp): input checks, the secret-scalar multiplication (constant-time kernel where the curve has
@@ -572,7 +638,7 @@ struct CurveOps {
     static const ecgpu_curve_ops t = {field_op, point_op, point_eq, normalize, lincomb, msm, validate_scalars, validate_points,
                                       decompress, synth_scalars, synth_points, to_bytes, from_bytes, sec1_encode, sec1_decode, ecdsa_verify, h2c_map, ecdsa_recover, schnorr_verify, ecdsa_sign, ecdh,
                                       pass_units, scalar_op, scalar_reduce, h2c_hash_to_field, field_from_okm, schnorr_challenge,
-                                      rfc6979_nonce, ecdsa_sign_prehash, schnorr_sign_prehash};
+                                      rfc6979_nonce, ecdsa_sign_prehash, schnorr_sign_prehash, schnorr_batch_verify};
     return &t;
   }
 };

@@ -9,7 +9,9 @@
 // (an absent optional buffer keeps its place in the count), or, for the calls that name a pass size and from PIPE_MIN elements
 // on, in chunks through the pipeline (host_pipe.hpp), list entry a of pipeline slot s in slot 6 + 6 s + a (a seventh entry: 25 + s).  What the list marks
 // secret is cleared from its slots (and from the pipeline's bounce buffers) before the call returns, whichever way it ends.
+#include <errno.h>
 #include <string.h>
+#include <sys/random.h>
 #include <condition_variable>
 #include <thread>
 #include <vector>
@@ -174,7 +176,7 @@ static const ecgpu_curve_ops* ops_for(int curve) {
 
 extern "C" {
 
-const char* ecgpu_version(void) { return "ecgpu 0.8 (gfx950)"; }
+const char* ecgpu_version(void) { return "ecgpu 0.9 (gfx950)"; }
 
 size_t ecgpu_field_bytes(int curve) {
   switch (curve) {
@@ -972,6 +974,124 @@ int ecgpu_schnorr_verify_msg_batch(ecgpu_ctx* c, int curve, const uint8_t* pubke
     if ((r = ops->schnorr_challenge(c, (const uint32_t*)d[0], (const uint32_t*)d[3], m, e, cnt))) return r;
     return ops->schnorr_verify(c, (const uint32_t*)d[0], (const uint32_t*)d[3], e, (uint8_t*)d[4], cnt);
   });
+}
+
+// ---------------------------------------------------------------------------------------------
+// BIP340 batch verification (include/ecgpu.h, "batch verification"; csrc/schnorr_batch_kernels.hpp).  Every chunk run_batch hands over
+// is one equation of its own (ops->schnorr_batch_verify), with the coefficients of its elements' indices in the caller's batch; the
+// verdict is the AND over the chunks.  Each equation synchronises the stream, so the chunks of a host batch of PIPE_MIN elements and
+// more do not overlap their copies with the kernels of the next one.  Nothing here is secret: nothing is wiped.
+// ---------------------------------------------------------------------------------------------
+struct SchnorrBatch {
+  ecgpu_ctx* c;
+  const ecgpu_curve_ops* ops;
+  unsigned flags;
+  bool equation;         // false: the per-signature pipeline (batches below ECGPU_SCHNORR_BATCH_MIN, where the equation does not win)
+  uint8_t seed[32];
+  size_t done = 0;       // elements of the chunks so far: run_batch launches them in order
+  int all = 1;
+  // one chunk whose challenges e are ready
+  int chunk(const void* px, const void* sig, const uint32_t* e, void* ok, size_t cnt) {
+    if (!equation) return ops->schnorr_verify(c, (const uint32_t*)px, (const uint32_t*)sig, e, (uint8_t*)ok, cnt);
+    int verdict = 0;
+    const int r = ops->schnorr_batch_verify(c, (const uint32_t*)px, (const uint32_t*)sig, e, (uint8_t*)ok, cnt, (uint64_t)done, seed, flags, &verdict);
+    if (r) return r;
+    done += cnt;
+    all &= verdict;
+    return 0;
+  }
+};
+// the checks the three forms share (before the context's lock is taken); *all_valid = 1 for the empty batch
+static int schnorr_batch_enter(ecgpu_ctx* c, int curve, const void* pubkeys_x, const void* sig_rs, const void* ok, int* all_valid, size_t n, unsigned flags) {
+  if (!c || !pubkeys_x || !sig_rs) return ecgpu_set_err(c, ECGPU_ERR_ARG, "null argument");
+  if (flags & ~(unsigned)(ECGPU_BATCH_VERDICT_ONLY | ECGPU_BATCH_EQUATION_ALWAYS)) return ecgpu_set_err(c, ECGPU_ERR_ARG, "ecgpu_schnorr_batch_verify: unknown flags 0x%x", flags);
+  if (!ok && !(flags & ECGPU_BATCH_VERDICT_ONLY)) return ecgpu_set_err(c, ECGPU_ERR_ARG, "ecgpu_schnorr_batch_verify: ok may be NULL with ECGPU_BATCH_VERDICT_ONLY only");
+  if (ecgpu_field_bytes(curve) && curve != ECGPU_K256)
+    return ecgpu_set_err(c, ECGPU_ERR_UNSUPPORTED, "ecgpu_schnorr_batch_verify: BIP340 is defined over secp256k1 only");
+  if (n == 0 && all_valid) *all_valid = 1;
+  return ECGPU_OK;
+}
+// routing and the seed (the caller's, or 32 bytes of getrandom(2))
+static int schnorr_batch_begin(SchnorrBatch& b, const uint8_t* seed32, const void* ok, size_t n) {
+  b.equation = (b.flags & ECGPU_BATCH_EQUATION_ALWAYS) || !ok || n >= ECGPU_SCHNORR_BATCH_MIN;
+  if (seed32) { memcpy(b.seed, seed32, 32); return 0; }
+  for (size_t got = 0; b.equation && got < 32;) {
+    const ssize_t r = getrandom(b.seed + got, 32 - got, 0);
+    if (r < 0 && errno == EINTR) continue;
+    if (r <= 0) return ecgpu_set_err(b.c, ECGPU_ERR_RUNTIME, "ecgpu_schnorr_batch_verify: getrandom failed (errno %d) and no seed was given", errno);
+    got += (size_t)r;
+  }
+  return 0;
+}
+// after run_batch: the stream is synchronised and the verdict handed out (per-signature routing: the AND over ok)
+static int schnorr_batch_end(SchnorrBatch& b, const uint8_t* ok, int* all_valid, size_t n, int mem) {
+  ecgpu_ctx* c = b.c;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (!b.equation) {
+    std::vector<uint8_t> copy;
+    if (mem == ECGPU_MEM_DEVICE) {
+      copy.resize(n);
+      HIPCHK(c, hipMemcpy(copy.data(), ok, n, hipMemcpyDeviceToHost));
+      ok = copy.data();
+    }
+    for (size_t i = 0; i < n; i++) b.all &= ok[i] == 1;
+  }
+  if (all_valid) *all_valid = b.all;
+  return ECGPU_OK;
+}
+static constexpr size_t SCHNORR_BATCH_PASS = (size_t)1 << 22;
+
+int ecgpu_schnorr_batch_verify(ecgpu_ctx* c, int curve, const uint8_t* pubkeys_x, const uint8_t* sig_rs, const uint8_t* challenges, const uint8_t* seed32,
+                               uint8_t* ok, int* all_valid, size_t n, int mem, unsigned flags) {
+  int rc = schnorr_batch_enter(c, curve, pubkeys_x, sig_rs, ok, all_valid, n, flags);
+  if (rc) return rc;
+  if (!challenges) return ecgpu_set_err(c, ECGPU_ERR_ARG, "null argument");
+  if (n == 0) return ECGPU_OK;
+  ENTER(c, curve);
+  SchnorrBatch b{c, ops, flags};
+  if ((rc = schnorr_batch_begin(b, seed32, ok, n))) return rc;
+  const CallArg args[] = {arg_in(pubkeys_x, nb), arg_in(sig_rs, 2 * nb), arg_in(challenges, nb), arg_out(ok, 1, ARG_OPTIONAL)};
+  rc = run_batch(c, mem, n, args, SCHNORR_BATCH_PASS, [&](void** d, size_t cnt) { return b.chunk(d[0], d[1], (const uint32_t*)d[2], d[3], cnt); });
+  return rc ? rc : schnorr_batch_end(b, ok, all_valid, n, mem);
+}
+int ecgpu_schnorr_batch_verify_prehash(ecgpu_ctx* c, int curve, const uint8_t* pubkeys_x, const uint8_t* sig_rs, const uint8_t* prehash, const uint8_t* seed32,
+                                       uint8_t* ok, int* all_valid, size_t n, int mem, unsigned flags) {
+  int rc = schnorr_batch_enter(c, curve, pubkeys_x, sig_rs, ok, all_valid, n, flags);
+  if (rc) return rc;
+  if (!prehash) return ecgpu_set_err(c, ECGPU_ERR_ARG, "null argument");
+  if (n == 0) return ECGPU_OK;
+  ENTER(c, curve);
+  SchnorrBatch b{c, ops, flags};
+  if ((rc = schnorr_batch_begin(b, seed32, ok, n))) return rc;
+  const CallArg args[] = {arg_in(pubkeys_x, nb), arg_in(sig_rs, 2 * nb), arg_in(prehash, 32), arg_out(ok, 1, ARG_OPTIONAL)};
+  rc = run_batch(c, mem, n, args, SCHNORR_BATCH_PASS, [&](void** d, size_t cnt) {
+    uint32_t* e;
+    int r = ecgpu_carve(c, c->hash_ws, [&](WsCarver& ws) { e = ws.take<uint32_t>(cnt * 32); });
+    if (r) return r;
+    if ((r = ops->schnorr_challenge(c, (const uint32_t*)d[0], (const uint32_t*)d[1], (const uint32_t*)d[2], e, cnt))) return r;
+    return b.chunk(d[0], d[1], e, d[3], cnt);
+  });
+  return rc ? rc : schnorr_batch_end(b, ok, all_valid, n, mem);
+}
+int ecgpu_schnorr_batch_verify_msg(ecgpu_ctx* c, int curve, const uint8_t* pubkeys_x, const uint8_t* msgs, size_t msg_stride, const uint32_t* msg_len,
+                                   const uint8_t* sig_rs, const uint8_t* seed32, uint8_t* ok, int* all_valid, size_t n, int mem, unsigned flags) {
+  int rc = schnorr_batch_enter(c, curve, pubkeys_x, sig_rs, ok, all_valid, n, flags);
+  if (rc) return rc;
+  if ((rc = msgs_enter(c, msgs, msg_stride, msg_len, n, mem))) return rc;
+  if (n == 0) return ECGPU_OK;
+  ENTER(c, curve);
+  SchnorrBatch b{c, ops, flags};
+  if ((rc = schnorr_batch_begin(b, seed32, ok, n))) return rc;
+  const CallArg args[] = {arg_in(pubkeys_x, nb), arg_in(msg_stride ? msgs : nullptr, msg_stride, ARG_OPTIONAL), arg_in(msg_len, 4, ARG_OPTIONAL),
+                          arg_in(sig_rs, 2 * nb), arg_out(ok, 1, ARG_OPTIONAL)};
+  rc = run_batch(c, mem, n, args, SCHNORR_BATCH_PASS, [&](void** d, size_t cnt) {
+    uint32_t *m, *e;
+    int r = digest_to_ws(c, curve, d[1], msg_stride, d[2], cnt, &m, &e);
+    if (r) return r;
+    if ((r = ops->schnorr_challenge(c, (const uint32_t*)d[0], (const uint32_t*)d[3], m, e, cnt))) return r;
+    return b.chunk(d[0], d[3], e, d[4], cnt);
+  });
+  return rc ? rc : schnorr_batch_end(b, ok, all_valid, n, mem);
 }
 
 int ecgpu_synth_scalars(ecgpu_ctx* c, int curve, uint64_t seed, uint64_t first, uint8_t* d_scalars, size_t n) {

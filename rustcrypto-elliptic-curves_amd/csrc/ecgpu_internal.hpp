@@ -202,7 +202,18 @@ struct ecgpu_curve_ops {
                             size_t n, unsigned flags);
   int (*schnorr_sign_prehash)(ecgpu_ctx* c, const uint32_t* d, const uint32_t* m, const uint32_t* aux, uint32_t* sig, uint32_t* pubkeys_x, uint8_t* ok,
                               size_t n);
+  // BIP340 batch verification (schnorr_batch_kernels.hpp; secp256k1 only): ONE equation over the n signatures, whose coefficients are those
+  // of elements first_index .. of the caller's batch under seed32 (32 bytes of HOST memory).  Synchronises the stream; *verdict = every
+  // element valid.  ok (NULL allowed with ECGPU_BATCH_VERDICT_ONLY) as include/ecgpu.h describes.
+  int (*schnorr_batch_verify)(ecgpu_ctx* c, const uint32_t* px, const uint32_t* sig, const uint32_t* e, uint8_t* ok, size_t n, uint64_t first_index,
+                              const uint8_t* seed32, unsigned flags, int* verdict);
 };
+// Signatures from which ecgpu_schnorr_batch_verify* takes the equation by default.  Under the MSM's small-sum limit (2n + 1 below
+// msm_kernels.hpp SMALL_MSM_TERMS; msm_k256.hip asserts the relation) the MSM is itself one multiplication per term and the equation
+// cannot win; measured, device-resident, equation against per-signature call (profiles/schnorr_batch_verify.txt): 2^16 1.71 / 1.73 ms
+// (inside the spread of the runs), 2^18 2.71 / 3.68 ms, 2^20 6.08 / 10.8 ms, 2^22 19.2 / 35.5 ms - 2^18 is the smallest measured size at
+// which it wins.
+constexpr size_t ECGPU_SCHNORR_BATCH_MIN = (size_t)1 << 18;
 // expand_message_xmd to raw bytes on `hash` (ecgpu_hash), curve-independent (h2c_hash.hip): out = n x tail.out_len bytes
 int ecgpuint_xmd(ecgpu_ctx* c, int hash, const uint8_t* msgs, size_t msg_stride, const uint32_t* msg_len, const ecgpu::h2c::XmdTail& tail, uint8_t* out, size_t n);
 // plain digests on `hash` (h2c_hash.hip): out = n rows of 32 / 48 bytes, 4-byte aligned

@@ -29,6 +29,7 @@ EXACT_REFERENCE = 1
 ECDSA_LOW_S = 2
 PUBLIC_SCALARS = 4
 SECRET_SCALARS = 8
+BATCH_VERDICT_ONLY, BATCH_EQUATION_ALWAYS = 16, 32                     # ecgpu_schnorr_batch_verify*
 K256, P256, P384 = 0, 1, 2
 CURVE_IDS = {"k256": K256, "p256": P256, "p384": P384}
 FIELD_BYTES = {K256: 32, P256: 32, P384: 48}
@@ -163,6 +164,9 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
     lib.ecgpu_ecdsa_recover_msg_batch.argtypes = [vp, i, u8p, sz, u8p, u8p, u8p, u8p, u8p, sz, i, ctypes.c_uint]
     lib.ecgpu_schnorr_sign_msg_batch.argtypes = [vp, i, u8p, u8p, sz, u8p, u8p, u8p, u8p, u8p, sz, i]
     lib.ecgpu_schnorr_verify_msg_batch.argtypes = [vp, i, u8p, u8p, sz, u8p, u8p, u8p, sz, i]
+    lib.ecgpu_schnorr_batch_verify.argtypes = [vp, i, u8p, u8p, u8p, u8p, u8p, ctypes.POINTER(i), sz, i, ctypes.c_uint]
+    lib.ecgpu_schnorr_batch_verify_prehash.argtypes = [vp, i, u8p, u8p, u8p, u8p, u8p, ctypes.POINTER(i), sz, i, ctypes.c_uint]
+    lib.ecgpu_schnorr_batch_verify_msg.argtypes = [vp, i, u8p, u8p, sz, u8p, u8p, u8p, u8p, ctypes.POINTER(i), sz, i, ctypes.c_uint]
     lib.ecgpu_synth_scalars.argtypes = [vp, i, ctypes.c_uint64, ctypes.c_uint64, u8p, sz]
     lib.ecgpu_synth_points.argtypes = [vp, i, ctypes.c_uint64, ctypes.c_uint64, u8p, sz]
     for name in ("ecgpu_create", "ecgpu_set_stream", "ecgpu_synchronize", "ecgpu_timer_start", "ecgpu_timer_stop",
@@ -179,7 +183,8 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
                  "ecgpu_group_msm", "ecgpu_group_msm_sharded", "ecgpu_schnorr_verify_prehash_batch", "ecgpu_expand_message_xmd_batch",
                  "ecgpu_field_from_okm_batch", "ecgpu_hash_to_curve_batch", "ecgpu_hash_to_scalar_batch", "ecgpu_rfc6979_nonce_batch",
                  "ecgpu_ecdsa_sign_prehash_batch", "ecgpu_schnorr_sign_prehash_batch", "ecgpu_digest_batch", "ecgpu_ecdsa_sign_msg_batch",
-                 "ecgpu_ecdsa_verify_msg_batch", "ecgpu_ecdsa_recover_msg_batch", "ecgpu_schnorr_sign_msg_batch", "ecgpu_schnorr_verify_msg_batch"):
+                 "ecgpu_ecdsa_verify_msg_batch", "ecgpu_ecdsa_recover_msg_batch", "ecgpu_schnorr_sign_msg_batch", "ecgpu_schnorr_verify_msg_batch",
+                 "ecgpu_schnorr_batch_verify", "ecgpu_schnorr_batch_verify_prehash", "ecgpu_schnorr_batch_verify_msg"):
         getattr(lib, name).restype = ctypes.c_int
     if path is None:
         _lib = lib
@@ -203,6 +208,7 @@ EXPORTED_SYMBOLS = (
     "ecgpu_hash_to_scalar_batch", "ecgpu_rfc6979_nonce_batch", "ecgpu_ecdsa_sign_prehash_batch", "ecgpu_schnorr_sign_prehash_batch",
     "ecgpu_digest_batch", "ecgpu_ecdsa_sign_msg_batch", "ecgpu_ecdsa_verify_msg_batch", "ecgpu_ecdsa_recover_msg_batch",
     "ecgpu_schnorr_sign_msg_batch", "ecgpu_schnorr_verify_msg_batch",
+    "ecgpu_schnorr_batch_verify", "ecgpu_schnorr_batch_verify_prehash", "ecgpu_schnorr_batch_verify_msg",
 )
 
 
@@ -853,6 +859,50 @@ class Curve:
         self.ctx.check(self.ctx.lib.ecgpu_schnorr_verify_msg_batch(self.ctx.handle, self.id, _ptr(x)[0], _ptr(rec)[0] if stride else None, stride, _ptr(lens)[0],
                                                                    _ptr(sg)[0], _ptr(ok)[0], len(x), HOST))
         return ok
+
+    # --- BIP340 batch verification: one equation per batch (include/ecgpu.h).  seed=None: the library draws one per call -------
+    @staticmethod
+    def _batch_seed(seed):
+        if seed is None:
+            return None
+        seed = bytes(seed)
+        if len(seed) != 32:
+            raise ValueError("the seed of a batch verification is 32 bytes")
+        return np.frombuffer(seed, dtype=np.uint8)
+
+    def _schnorr_batch_host(self, fn, pubkeys_x, sig_rs, third, seed, flags: int):
+        x, sg, t = _as_host(pubkeys_x, self.nb), _as_host(sig_rs, 2 * self.nb), _as_host(third, 32)
+        if not (len(x) == len(sg) == len(t)):
+            raise ValueError("key, signature and challenge / prehash batches differ in length")
+        ok, all_valid, sd = np.zeros(len(x), dtype=np.uint8), ctypes.c_int(0), self._batch_seed(seed)
+        self.ctx.check(fn(self.ctx.handle, self.id, _ptr(x)[0], _ptr(sg)[0], _ptr(t)[0], _ptr(sd)[0], _ptr(ok)[0], ctypes.byref(all_valid), len(x), HOST, flags))
+        return ok, bool(all_valid.value)
+
+    def schnorr_batch_verify(self, pubkeys_x, sig_rs, challenges, seed=None, flags: int = 0):
+        """BIP340 batch verification from the challenge hashes -> (ok, all_valid)"""
+        return self._schnorr_batch_host(self.ctx.lib.ecgpu_schnorr_batch_verify, pubkeys_x, sig_rs, challenges, seed, flags)
+
+    def schnorr_batch_verify_prehash(self, pubkeys_x, sig_rs, prehashes, seed=None, flags: int = 0):
+        """BIP340 batch verification from the 32-byte digests -> (ok, all_valid); ok as schnorr_verify_prehash gives it"""
+        return self._schnorr_batch_host(self.ctx.lib.ecgpu_schnorr_batch_verify_prehash, pubkeys_x, sig_rs, prehashes, seed, flags)
+
+    def schnorr_batch_verify_prehash_device(self, d_pubkeys_x, d_sig_rs, d_prehash, d_ok, n: int, seed=None, flags: int = 0):
+        """device-resident batch (d_ok may be None with BATCH_VERDICT_ONLY) -> (d_ok, all_valid); the call synchronises the stream"""
+        all_valid, sd = ctypes.c_int(0), self._batch_seed(seed)
+        self.ctx.check(self.ctx.lib.ecgpu_schnorr_batch_verify_prehash(self.ctx.handle, self.id, _ptr(d_pubkeys_x)[0], _ptr(d_sig_rs)[0], _ptr(d_prehash)[0],
+                                                                       _ptr(sd)[0], _ptr(d_ok)[0], ctypes.byref(all_valid), n, DEVICE, flags))
+        return d_ok, bool(all_valid.value)
+
+    def schnorr_batch_verify_msg(self, pubkeys_x, msgs: Sequence[bytes], sig_rs, seed=None, flags: int = 0):
+        """BIP340 batch verification over SHA256(msg) -> (ok, all_valid)"""
+        x, sg = _as_host(pubkeys_x, self.nb), _as_host(sig_rs, 2 * self.nb)
+        if not (len(x) == len(sg) == len(msgs)):
+            raise ValueError("key, message and signature batches differ in length")
+        rec, lens, stride = pack_messages_aligned(msgs)
+        ok, all_valid, sd = np.zeros(len(x), dtype=np.uint8), ctypes.c_int(0), self._batch_seed(seed)
+        self.ctx.check(self.ctx.lib.ecgpu_schnorr_batch_verify_msg(self.ctx.handle, self.id, _ptr(x)[0], _ptr(rec)[0] if stride else None, stride, _ptr(lens)[0],
+                                                                   _ptr(sg)[0], _ptr(sd)[0], _ptr(ok)[0], ctypes.byref(all_valid), len(x), HOST, flags))
+        return ok, bool(all_valid.value)
 
     # --- synthetic inputs (device buffers) ---------------------------------------------------------
     def synth_scalars_device(self, d_out, n: int, seed: int, first_index: int = 0):

@@ -45,6 +45,18 @@ def verify_batch_device(curve: Curve, pubkeys_x: Sequence[bytes], prehashes: Seq
     return curve.schnorr_verify_prehash(b"".join(pubkeys_x), b"".join(sigs), b"".join(prehashes))
 
 
+def batch_verify_device(curve: Curve, pubkeys_x: Sequence[bytes], prehashes: Sequence[bytes], sigs: Sequence[bytes], seed: bytes | None = None,
+                        flags: int = 0):
+    """BIP340 batch verification (ecgpu_schnorr_batch_verify_prehash): one multi-scalar multiplication for the batch instead of two
+    multiplications per signature -> (ok, all_valid), ok as verify_batch_device gives it.  seed=None lets the library draw the 32
+    bytes the coefficients come from; a caller's seed must be unpredictable to whoever made the signatures."""
+    if curve.id != K256:
+        raise ValueError("BIP340 is defined over secp256k1")
+    if any(len(m) != 32 for m in prehashes):
+        raise ValueError("verify_prehash takes 32-byte digests")     # verifying.rs:68
+    return curve.schnorr_batch_verify_prehash(b"".join(pubkeys_x), b"".join(sigs), b"".join(prehashes), seed=seed, flags=flags)
+
+
 def sign_batch(curve: Curve, secret_keys: Sequence[bytes], prehashes: Sequence[bytes], aux_rands: Sequence[bytes]):
     """sign_prehash_with_aux_rand (signing.rs:80-131) for a batch -> (signatures, public keys x-only)."""
     if curve.id != K256:

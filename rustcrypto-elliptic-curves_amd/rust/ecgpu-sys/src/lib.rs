@@ -61,6 +61,9 @@ pub const ECGPU_PUBLIC_SCALARS: c_uint = 4;
 /// secret scalars, group element only: constant-time fixed base for k G (key generation); for a variable base (ECDH) the
 /// constant-time kernels of csrc/varbase_ct.hpp (P-256 / P-384) and csrc/varbase_ct_k256.hpp (secp256k1)
 pub const ECGPU_SECRET_SCALARS: c_uint = 8;
+/// flags of `ecgpu_schnorr_batch_verify*`: no per-signature fallback / the equation at every batch size
+pub const ECGPU_BATCH_VERDICT_ONLY: c_uint = 16;
+pub const ECGPU_BATCH_EQUATION_ALWAYS: c_uint = 32;
 /// `ecgpu_option`: per-context tuning / test knobs (the library never reads the process environment)
 pub const ECGPU_OPT_FB_WINDOW: c_int = 0;
 pub const ECGPU_OPT_FB_MAX_WINDOW: c_int = 1;
@@ -161,6 +164,12 @@ extern "C" {
                                         aux_rand: *const u8, sig_rs: *mut u8, pubkeys_x: *mut u8, ok: *mut u8, n: usize, mem: c_int) -> c_int;
     pub fn ecgpu_schnorr_verify_msg_batch(ctx: *mut ecgpu_ctx, curve: c_int, pubkeys_x: *const u8, msgs: *const u8, msg_stride: usize, msg_len: *const u32,
                                           sig_rs: *const u8, ok: *mut u8, n: usize, mem: c_int) -> c_int;
+    pub fn ecgpu_schnorr_batch_verify(ctx: *mut ecgpu_ctx, curve: c_int, pubkeys_x: *const u8, sig_rs: *const u8, challenges: *const u8, seed32: *const u8,
+                                      ok: *mut u8, all_valid: *mut c_int, n: usize, mem: c_int, flags: c_uint) -> c_int;
+    pub fn ecgpu_schnorr_batch_verify_prehash(ctx: *mut ecgpu_ctx, curve: c_int, pubkeys_x: *const u8, sig_rs: *const u8, prehash: *const u8, seed32: *const u8,
+                                              ok: *mut u8, all_valid: *mut c_int, n: usize, mem: c_int, flags: c_uint) -> c_int;
+    pub fn ecgpu_schnorr_batch_verify_msg(ctx: *mut ecgpu_ctx, curve: c_int, pubkeys_x: *const u8, msgs: *const u8, msg_stride: usize, msg_len: *const u32,
+                                          sig_rs: *const u8, seed32: *const u8, ok: *mut u8, all_valid: *mut c_int, n: usize, mem: c_int, flags: c_uint) -> c_int;
     pub fn ecgpu_group_create(group: *mut *mut ecgpu_group, devices: *const c_int, n_devices: c_int, flags: c_uint) -> c_int;
     pub fn ecgpu_group_destroy(group: *mut ecgpu_group);
     pub fn ecgpu_group_size(group: *const ecgpu_group) -> c_int;
@@ -600,6 +609,19 @@ impl Context {
             ecgpu_schnorr_verify_prehash_batch(self.0, ECGPU_K256, pubkeys_x.as_ptr(), sig_rs.as_ptr(), prehashes.as_ptr(), ok.as_mut_ptr(), ok.len(), ECGPU_MEM_HOST)
         })?;
         Ok(ok)
+    }
+    /// BIP340 batch verification: one multi-scalar multiplication for the batch -> (ok as `schnorr_verify_prehash` gives it, all valid).
+    /// `seed`: `None` lets the library draw the 32 bytes its coefficients come from (a caller's seed must be unpredictable to whoever
+    /// made the signatures); `flags`: `ECGPU_BATCH_VERDICT_ONLY` | `ECGPU_BATCH_EQUATION_ALWAYS`.
+    pub fn schnorr_batch_verify_prehash(&self, pubkeys_x: &[u8], sig_rs: &[u8], prehashes: &[u8], seed: Option<&[u8; 32]>, flags: c_uint) -> Result<(Vec<u8>, bool), Error> {
+        Self::arg(pubkeys_x.len() % 32 == 0 && sig_rs.len() == 2 * pubkeys_x.len() && prehashes.len() == pubkeys_x.len())?;
+        let mut ok = vec![0u8; pubkeys_x.len() / 32];
+        let mut all_valid: c_int = 0;
+        self.check(unsafe {
+            ecgpu_schnorr_batch_verify_prehash(self.0, ECGPU_K256, pubkeys_x.as_ptr(), sig_rs.as_ptr(), prehashes.as_ptr(), seed.map_or(core::ptr::null(), |s| s.as_ptr()),
+                                               ok.as_mut_ptr(), &mut all_valid, ok.len(), ECGPU_MEM_HOST, flags)
+        })?;
+        Ok((ok, all_valid != 0))
     }
     /// ToEncodedPoint::to_encoded_point(compress) in fixed-width records (identity: tag 0x00 and zero padding)
     pub fn sec1_encode(&self, curve: c_int, points: &[u8], point_format: c_int, compress: bool) -> Result<Vec<u8>, Error> {

@@ -143,6 +143,14 @@ pub fn schnorr_verify_prehash_batch(gpu: &Context, pubkeys_x: &[[u8; 32]], preha
     let ok = gpu.schnorr_verify_prehash(&pubkeys_x.concat(), &sigs.concat(), &prehashes.concat())?;
     Ok(ok.into_iter().map(|f| f != 0).collect())
 }
+/// The same answers from BIP340's batch equation (one multi-scalar multiplication over 2n + 1 terms; the per-signature pipeline
+/// runs only for a batch that holds an invalid signature) -> (per-signature flags, all valid).  The library draws the seed of the
+/// equation's coefficients itself.
+pub fn schnorr_batch_verify_prehash(gpu: &Context, pubkeys_x: &[[u8; 32]], prehashes: &[[u8; 32]], sigs: &[[u8; 64]]) -> Result<(Vec<bool>, bool), Error> {
+    assert!(pubkeys_x.len() == prehashes.len() && prehashes.len() == sigs.len());
+    let (ok, all_valid) = gpu.schnorr_batch_verify_prehash(&pubkeys_x.concat(), &sigs.concat(), &prehashes.concat(), None, 0)?;
+    Ok((ok.into_iter().map(|f| f != 0).collect(), all_valid))
+}
 
 /// `PrehashSigner<Signature>::sign_prehash` of `ecdsa::SigningKey<Secp256k1>` for many (key, digest) pairs: RFC 6979 nonces
 /// (HMAC-DRBG on SHA-256), k G on the constant-time kernel, low-s normalisation as ecdsa.rs:182-196.  `digests`: after bits2field
