@@ -104,12 +104,14 @@ ECGPU_HD void jac_double_affine(JacK256& r, const FeK256& x, const FeK256& y) {
 
 ECGPU_HD bool z_is_one(const FeK256& z) { FeK256 o; set_one(o); return equal(z, o); }   // for the ECGPU_EXC_NOTE conditions only
 
-// In-place p += (x2, y2) for an affine, non-identity (x2, y2).  8M + 3S.  `zr` (optional) receives
-// the ratio Z3 / Z1 = H, which the table construction needs.  Real control flow (not selects) for
+// In-place p += (x2, y2) for an affine, non-identity (x2, y2).  8M + 3S.  Real control flow (not selects) for
 // the special cases so that no second copy of the accumulator has to stay live:
 //   p at infinity            -> (x2, y2, 1)
-//   same x, same y (H=R=0)   -> doubling of (x2, y2)
+//   same x, same y (H=R=0)   -> doubling of (x2, y2); with `zr`, doubling of p itself (the same point over Z3 = 2 Y1 Z1)
 //   same x, opposite y       -> Z3 = Z1 * 0 = 0: infinity falls out of the formula
+// `zr` (optional) receives the ratio Z3 / Z1, which a table construction over one denominator needs: H, 2 Y1 in the same-point
+// case, and 1 for p at infinity, which has no ratio.  Every caller in the kernels passes nullptr, so the `zr` paths run in the
+// tests alone (tests/devtwin/group_ops.hpp runs the formula both ways over the same operands).
 ECGPU_HD void jac_add_mixed(JacK256& p, const FeK256& x2, const FeK256& y2, FeK256* zr) {
   if (is_zero_fast(p.z)) {
     ECGPU_EXC_NOTE("k256.jac_add_mixed.inf", true);
@@ -126,7 +128,11 @@ ECGPU_HD void jac_add_mixed(JacK256& p, const FeK256& x2, const FeK256& y2, FeK2
   if (__builtin_expect(is_zero_fast(h) && is_zero(r), 0)) {   // never taken for honest GLV digits; kept exact
     ECGPU_EXC_NOTE("k256.jac_add_mixed.same", true);
     ECGPU_EXC_NOTE("k256.jac_add_mixed.same:z", !z_is_one(p.z));
-    if (zr) dbl(*zr, y2);
+    if (zr) {                                // the ratio is wanted: double p itself, Z3 = 2 Y1 Z1 (2 y2 is the ratio only for Z1 = 1)
+      dbl(*zr, p.y);
+      jac_double(p);
+      return;
+    }
     jac_double_affine(p, x2, y2);
     return;
   }

@@ -1,5 +1,5 @@
-"""Loader for the test-only gfx950 build of the field and scalar primitives (tests/devtwin) and its host counterpart
-(tests/hosttwin, the same op tables).  Arrays are (n, words) little-endian uint32; every call checks the return code and
+"""Loader for the test-only gfx950 builds of the field and scalar primitives, the point formulas and the RFC 6979 generator
+(tests/devtwin) and their host counterpart (tests/hosttwin, the same op tables).  Arrays are (n, words) little-endian uint32; every call checks the return code and
 raises at the first non-zero one."""
 import ctypes
 import os
@@ -9,7 +9,9 @@ import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 DEVTWIN = os.path.join(HERE, "devtwin")
-BUILDS = {"default": "libecdevtwin.so", "bf": "libecdevtwin_bf.so", "grouped": "libecdevtwin_grouped.so"}
+BUILDS = {"default": "libecdevtwin.so", "bf": "libecdevtwin_bf.so", "grouped": "libecdevtwin_grouped.so",
+          # the point formulas (devtwin_group.hip) in the two configurations that ship them, and the RFC 6979 generator
+          "group": "libecdevtwin_group.so", "group_bf": "libecdevtwin_group_bf.so", "rfc6979": "libecdevtwin_rfc6979.so"}
 _LIBS = {}
 
 # op tables of tests/devtwin/primitive_ops.hpp
@@ -26,7 +28,7 @@ _P = ctypes.POINTER(ctypes.c_uint32)
 
 def lib(build="default"):
     if build not in _LIBS:
-        override = os.environ.get("ECGPU_DEVTWIN_DIR")     # the same three objects built elsewhere (e.g. from a patched csrc)
+        override = os.environ.get("ECGPU_DEVTWIN_DIR")     # the same objects built elsewhere (e.g. from a patched csrc)
         if override:
             _LIBS[build] = ctypes.CDLL(os.path.join(override, BUILDS[build]))
         else:
@@ -97,3 +99,33 @@ def host():
     from hosttwin_util import lib as hlib
     L = hlib()
     return {"k256": L.ht_k256_prim_op, "mont": L.ht_mont_prim_op, "scalar": L.ht_scalar_op, "mac": L.ht_mac_cols}
+
+
+# the point-formula op table (tests/devtwin/group_ops.hpp; callers: tests/group_edge_vectors.py run())
+def device_pt_op(build="group"):
+    assert build in ("group", "group_bf")
+    return lib(build).dt_pt_op
+
+
+def host_pt_op():
+    from hosttwin_util import lib as hlib
+    return hlib().ht_pt_op
+
+
+def rfc6979_generate_k(hash_id, xs, h1s, extras, q):
+    """dt_rfc6979_generate_k over lists of byte strings (big-endian, one digest long; extras: b"" where a lane has none) and the
+    order q -> ([k], [rejections])"""
+    nw = 8 if hash_id == 0 else 12
+    n = len(xs)
+    limbs = lambda bs, w: np.frombuffer(b"".join(int.from_bytes(b, "big").to_bytes(4 * w, "little") for b in bs), dtype="<u4").reshape(len(bs), w).astype(np.uint32)
+    x, h1 = limbs(xs, nw), limbs(h1s, nw)
+    ex = np.zeros((n, nw + 1), dtype=np.uint32)
+    ex[:, :nw] = limbs([e or bytes(4 * nw) for e in extras], nw)
+    ex[:, nw] = [1 if e else 0 for e in extras]
+    qw = limbs([q.to_bytes(4 * nw, "big")], nw)
+    k = np.zeros((n, nw), dtype=np.uint32)
+    rej = np.zeros(n, dtype=np.uint32)
+    _check(lib("rfc6979").dt_rfc6979_generate_k(hash_id, _ptr(x), _ptr(h1), _ptr(ex) if any(extras) else None, _ptr(qw), _ptr(k), _ptr(rej), n),
+           "rfc6979 generate_k")
+    raw = np.ascontiguousarray(k, dtype="<u4").tobytes()
+    return [int.from_bytes(raw[4 * nw * i:4 * nw * (i + 1)], "little") for i in range(n)], [int(r) for r in rej]

@@ -94,7 +94,9 @@ def test_msm(ctx, cn, path, n, slab):
     every run) reach the XYZZ same-point and opposite-point branches by construction, but only with ZZ = 1 (the second entry of a
     run, or the one after a restart).  The hits with ZZ != 1 in the bucket runs, in the tree of running sums and in the Horner step
     rest on the other designs ("walk_*": partial sums walk over the multiples that are added; "window_shift": related buckets in
-    neighbouring windows; "cancel"): likely, not measured."""
+    neighbouring windows; "cancel").  Those branches themselves run on the device, with ZZ = 2, p - 1 and random and with lanes of
+    one wave in different branches, in tests/test_gpu_group_edges.py (msm::xyzz_add_mixed, xyzz_add and jac::add one pair per lane;
+    tests/test_hosttwin_group_edges.py counts the ":z" sites its vectors reach)."""
     cv = ctx.curve(cn)
     try:
         _set_path(ctx, path, slab)
