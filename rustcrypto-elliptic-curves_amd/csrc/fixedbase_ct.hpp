@@ -2,7 +2,7 @@
 // table entries it reads).  See fixedbase.hpp (mul_ct_kernel) for the schedule and its place in the library.
 #pragma once
 #include "jacobian.hpp"
-#include "varbase_ct.hpp"        // fe_mask_select
+#include "varbase_ct.hpp"        // the masks
 #include "msm.hpp"               // Xyzz
 
 namespace ecgpu {
@@ -30,6 +30,27 @@ ECGPU_HD void xyzz_add_mixed_raw(msm::Xyzz<C>& p, const typename C::Fe& x2, cons
   C::fe_mul(t, p.y, t);                                      // Y1 PPP
   C::fe_sub(q, q, p.x); C::fe_mul(q, r, q);                  // R (Q - X3)
   C::fe_sub(p.y, q, t);                                      // (the fused difference of products, C::fe_mul_sub2, costs this kernel registers: k256 signing 4.79 against 4.53 ms per 2^20)
+}
+
+// acc += (qx, qy) for every digit, the XYZZ form of vbct::ct_accumulate: `mag` is the digit's magnitude (zero: acc is kept), `empty` all
+// ones while acc is still O (the result is then the entry itself).  Both become masks; the addition itself always executes.  (The
+// zero-digit mask is formed in here from the magnitude: passed in as a mask, the same statements cost the secp256k1 kernel three more
+// spilled registers and 1 % of its time, profiles/ct_shared_primitives.txt.)
+template <class C>
+ECGPU_HD void xyzz_ct_accumulate(msm::Xyzz<C>& acc, u32& empty, const typename C::Fe& qx, const typename C::Fe& qy, u32 mag, const typename C::Fe& one) {
+  const u32 zd = vbct::mask_eq(mag, 0u);                                         // all ones iff the digit is zero
+  msm::Xyzz<C> t = acc;
+  xyzz_add_mixed_raw<C>(t, qx, qy);                                              // garbage for an empty accumulator or a zero digit
+  const u32 take_q = empty & ~zd;                                                // first non-zero digit: the entry itself
+  vbct::fe_mask_select<C>(t.x, take_q, qx, t.x);
+  vbct::fe_mask_select<C>(t.y, take_q, qy, t.y);
+  vbct::fe_mask_select<C>(t.zz, take_q, one, t.zz);
+  vbct::fe_mask_select<C>(t.zzz, take_q, one, t.zzz);
+  vbct::fe_mask_select<C>(acc.x, zd, acc.x, t.x);
+  vbct::fe_mask_select<C>(acc.y, zd, acc.y, t.y);
+  vbct::fe_mask_select<C>(acc.zz, zd, acc.zz, t.zz);
+  vbct::fe_mask_select<C>(acc.zzz, zd, acc.zzz, t.zzz);
+  empty &= zd;
 }
 
 // acc = k G for a scalar k < n (reduced by the caller), returned in the reference's homogeneous projective coordinates.
@@ -76,7 +97,7 @@ ECGPU_HD void mul_ct_one(typename C::Pt& out, const u32* k, const AffEntry<C>* t
     const u32 v = ((u32)(pair >> sh) & ((1u << CT_WB) - 1u)) + carry;            // 0 .. 32
     carry = (j == NWIN - 1) ? 0u : ((v + (1u << (CT_WB - 1))) >> CT_WB);         // v >= 16 -> v - 32 and a carry; the top window keeps v
     const int d = (int)v - (int)(carry << CT_WB);                                // -16 .. 16
-    const u32 sgn = (u32)(d >> 31), mag = ((u32)d ^ sgn) - sgn;                  // |d| without a branch
+    const vbct::SignMag dg = vbct::sign_mag(d);
     Fe qx, qy;
     C::fe_zero(qx);
     C::fe_zero(qy);
@@ -84,27 +105,15 @@ ECGPU_HD void mul_ct_one(typename C::Pt& out, const u32* k, const AffEntry<C>* t
 #pragma unroll 4
     for (int e = 0; e < CT_ENTRIES; e++) {
       ECGPU_TABLE_TOUCH(j * CT_ENTRIES + e);
-      const u32 mk = 0u - (((mag ^ (u32)(e + 1)) - 1u) >> 31);                   // all ones iff mag == e + 1
+      const u32 mk = vbct::mask_eq(dg.mag, (u32)(e + 1));
       const AffEntry<C> t = row[e];
 #pragma unroll
       for (int w = 0; w < NW; w++) { qx.v[w] |= t.x.v[w] & mk; qy.v[w] |= t.y.v[w] & mk; }
     }
     Fe ny;
     C::fe_neg(ny, qy);
-    vbct::fe_mask_select<C>(qy, sgn, ny, qy);
-    const u32 zd = 0u - ((mag - 1u) >> 31);                                      // all ones iff the digit is zero
-    msm::Xyzz<C> t = acc;
-    xyzz_add_mixed_raw<C>(t, qx, qy);                                            // garbage for an empty accumulator or a zero digit
-    const u32 take_q = empty & ~zd;                                              // first non-zero digit: the entry itself
-    vbct::fe_mask_select<C>(t.x, take_q, qx, t.x);
-    vbct::fe_mask_select<C>(t.y, take_q, qy, t.y);
-    vbct::fe_mask_select<C>(t.zz, take_q, one, t.zz);
-    vbct::fe_mask_select<C>(t.zzz, take_q, one, t.zzz);
-    vbct::fe_mask_select<C>(acc.x, zd, acc.x, t.x);
-    vbct::fe_mask_select<C>(acc.y, zd, acc.y, t.y);
-    vbct::fe_mask_select<C>(acc.zz, zd, acc.zz, t.zz);
-    vbct::fe_mask_select<C>(acc.zzz, zd, acc.zzz, t.zzz);
-    empty &= zd;
+    vbct::fe_mask_select<C>(qy, dg.sgn, ny, qy);
+    xyzz_ct_accumulate<C>(acc, empty, qx, qy, dg.mag, one);
   }
   // XYZZ (X, Y, ZZ, ZZZ) = homogeneous (X ZZZ : Y ZZ : ZZ ZZZ); k = 0 (all coordinates still zero): the identity (0 : 1 : 0)
   Fe y;

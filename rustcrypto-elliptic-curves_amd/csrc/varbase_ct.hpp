@@ -79,19 +79,31 @@ ECGPU_HD void jac_st(const LaneMem& m, int chunk, const Jac<C>& p) {
   fe_st<C>(m, chunk, p.x); fe_st<C>(m, chunk + cw<C>(), p.y); fe_st<C>(m, chunk + 2 * cw<C>(), p.z);
 }
 
+// ---- the masks of the three constant-time kernels (this file, varbase_ct_k256.hpp, fixedbase_ct.hpp): words that are all ones or zero
+ECGPU_HD u32 mask_zero(u32 v) { return 0u - (((v | (0u - v)) >> 31) ^ 1u); }        // all ones iff v == 0
+ECGPU_HD u32 mask_eq(u32 a, u32 b) { return 0u - (((a ^ b) - 1u) >> 31); }          // all ones iff a == b; a, b < 2^31 (digits, entry numbers)
+ECGPU_HD u32 mask_bit(u32 bits, int b) { return 0u - ((bits >> b) & 1u); }          // all ones iff bit b is set
+// a signed digit as its sign (a mask) and its magnitude, without a branch
+struct SignMag { u32 sgn, mag; };
+ECGPU_HD SignMag sign_mag(int d) {
+  const u32 sgn = (u32)(d >> 31);
+  return {sgn, ((u32)d ^ sgn) - sgn};
+}
 // r = mk ? a : b word by word, mk all ones or zero.  Arithmetic masks on purpose (see fixedbase_ct.hpp).
 template <class C>
 ECGPU_HD void fe_mask_select(typename C::Fe& r, u32 mk, const typename C::Fe& a, const typename C::Fe& b) {
 #pragma unroll
   for (int w = 0; w < C::NW; w++) r.v[w] = (a.v[w] & mk) | (b.v[w] & ~mk);
 }
-// all ones iff the field element is zero (fully reduced representations: the NIST fields)
+// all ones iff the field element is zero (fully reduced representations: the NIST fields; varbase_ct_k256.hpp specialises it for
+// the weakly reduced secp256k1 field)
 template <class C>
 ECGPU_HD u32 fe_zero_mask(const typename C::Fe& a) {
+  static_assert(!C::A_IS_ZERO, "secp256k1's zero has two word strings: include varbase_ct_k256.hpp");
   u32 t = 0;
 #pragma unroll
   for (int w = 0; w < C::NW; w++) t |= a.v[w];
-  return 0u - (((t | (0u - t)) >> 31) ^ 1u);
+  return mask_zero(t);
 }
 
 // p += (x2, y2) by the plain Jacobian mixed addition, 8M + 3S, NO exceptional-case handling: valid iff p is finite and
@@ -114,6 +126,27 @@ ECGPU_HD void add_mixed_raw(Jac<C>& p, const typename C::Fe& x2, const typename 
   C::fe_sub(t, t, p.x); C::fe_mul(t, r, t);
   C::fe_mul(h, p.y, h);
   C::fe_sub(p.y, t, h);
+}
+// "Add for every digit, then resolve by masks": `sum` is acc + (qx, qy) by the curve's raw addition, garbage for an empty accumulator
+// or a zero digit.  `zd` is all ones iff the digit is zero (acc is kept), `empty` all ones while acc is still O (the result is then
+// the entry itself).  Both are masks, updated from the digits, never a test of Z.
+template <class C, class Acc>
+ECGPU_HD void ct_resolve(Acc& acc, Acc& sum, u32& empty, const typename C::Fe& qx, const typename C::Fe& qy, u32 zd, const typename C::Fe& one) {
+  const u32 take_q = empty & ~zd;                                                    // first non-zero digit
+  fe_mask_select<C>(sum.x, take_q, qx, sum.x);
+  fe_mask_select<C>(sum.y, take_q, qy, sum.y);
+  fe_mask_select<C>(sum.z, take_q, one, sum.z);
+  fe_mask_select<C>(acc.x, zd, acc.x, sum.x);
+  fe_mask_select<C>(acc.y, zd, acc.y, sum.y);
+  fe_mask_select<C>(acc.z, zd, acc.z, sum.z);
+  empty &= zd;
+}
+// acc += (qx, qy) for every digit; the addition itself always executes.  (secp256k1: k256_ct_accumulate, varbase_ct_k256.hpp.)
+template <class C>
+ECGPU_HD void ct_accumulate(Jac<C>& acc, u32& empty, const typename C::Fe& qx, const typename C::Fe& qy, u32 zd, const typename C::Fe& one) {
+  Jac<C> t = acc;
+  add_mixed_raw<C>(t, qx, qy);
+  ct_resolve<C>(acc, t, empty, qx, qy, zd, one);
 }
 // k' = min(k mod n, n - k mod n) and the mask of the flip, branch-free
 template <class C>
@@ -139,6 +172,97 @@ ECGPU_HD u32 scalar_fold(u32* k, const u32* be) {
   return flip;
 }
 
+// The prologue of a unit: the input point (public data) in either wire format as Jacobian (x, y, z), and the mask of an identity
+// input.  That input is replaced by G under the mask, so that the arithmetic stays on a valid point; the caller forces the result
+// to the identity later.
+template <class C>
+ECGPU_HD u32 load_point(typename C::Fe& x, typename C::Fe& y, typename C::Fe& z, const u32* src, int pt_fmt, const typename C::Fe& one) {
+  constexpr int NW = C::NW;
+  C::fe_load(x, src);
+  C::fe_load(y, src + NW);
+  u32 inf_mask;
+  if (pt_fmt == FMT_PROJECTIVE) {              // public: the wire format
+    C::fe_load(z, src + 2 * NW);
+    inf_mask = fe_zero_mask<C>(z);
+    typename C::Fe zz;
+    C::fe_mul(x, x, z);                        // homogeneous (X : Y : Z) is Jacobian (X Z : Y Z^2 : Z)
+    C::fe_sqr(zz, z);
+    C::fe_mul(y, y, zz);
+  } else {
+    u32 t = 0;
+#pragma unroll
+    for (int w = 0; w < 2 * NW; w++) t |= src[w];
+    inf_mask = mask_zero(t);
+    z = one;
+  }
+  typename C::Pt g;
+  C::pt_generator(g);
+  fe_mask_select<C>(x, inf_mask, g.x, x);
+  fe_mask_select<C>(y, inf_mask, g.y, y);
+  fe_mask_select<C>(z, inf_mask, one, z);
+  return inf_mask;
+}
+
+// The epilogue of a pass: x = X / Z^2, y = Y / Z^3 with one inversion for the cnt results of this lane, stored in either wire format.
+// Slot b's Jacobian result is parked at chunk res_chunk(b) (x, y, z), its prefix product goes to pre_chunk(b); bit b of res_inf
+// says that result b is the identity.
+template <class C, class ResChunk, class PreChunk>
+ECGPU_HD void store_results(u32* out, int out_fmt, uint8_t* out_inf, size_t base, size_t T, const LaneMem& ws, int cnt, u32 res_inf,
+                            ResChunk res_chunk, PreChunk pre_chunk) {
+  constexpr int NW = C::NW, CW = cw<C>();
+  using Fe = typename C::Fe;
+  Fe one, zero;
+  C::fe_one(one); C::fe_zero(zero);
+  Fe run = one;
+#pragma unroll 1
+  for (int b = 0; b < cnt; b++) {
+    Fe z;
+    fe_st<C>(ws, pre_chunk(b), run);
+    fe_ld<C>(z, ws, res_chunk(b) + 2 * CW);
+    // Z = 0 besides the tracked identities: only for input that is not on the curve (a small-order point of another cubic makes the raw
+    // addition meet acc = +-Q).  It must not reach the shared product: fe_inv(0) = 0 would wipe every result of this lane's pass.
+    const u32 zm = fe_zero_mask<C>(z) | mask_bit(res_inf, b);
+    res_inf |= (zm & 1u) << b;
+    fe_mask_select<C>(z, zm, one, z);
+    C::fe_mul(run, run, z);
+  }
+  Fe inv;
+  C::fe_inv(inv, run);
+#pragma unroll 1
+  for (int b = cnt - 1; b >= 0; b--) {
+    const size_t i = base + (size_t)b * T;
+    const u32 inf = mask_bit(res_inf, b);
+    Fe z, pre, zi, t, x, yv;
+    fe_ld<C>(z, ws, res_chunk(b) + 2 * CW);
+    fe_mask_select<C>(z, inf, one, z);
+    fe_ld<C>(pre, ws, pre_chunk(b));
+    C::fe_mul(zi, inv, pre);
+    C::fe_mul(inv, inv, z);
+    C::fe_sqr(t, zi);
+    fe_ld<C>(x, ws, res_chunk(b));
+    C::fe_mul(x, x, t);
+    C::fe_mul(t, t, zi);
+    fe_ld<C>(yv, ws, res_chunk(b) + CW);
+    C::fe_mul(yv, yv, t);
+    // the parked result and its prefix product are secrets of the same rank as the output: they do not stay in the workspace
+    fe_st<C>(ws, res_chunk(b), zero); fe_st<C>(ws, res_chunk(b) + CW, zero); fe_st<C>(ws, res_chunk(b) + 2 * CW, zero);
+    fe_st<C>(ws, pre_chunk(b), zero);
+    fe_mask_select<C>(x, inf, zero, x);
+    if (out_fmt == FMT_PROJECTIVE) {          // public: the wire format.  (x : y : 1), identity (0 : 1 : 0)
+      Fe zo;
+      fe_mask_select<C>(yv, inf, one, yv);
+      fe_mask_select<C>(zo, inf, zero, one);
+      u32* o = out + i * 3 * NW;
+      C::fe_store(o, x); C::fe_store(o + NW, yv); C::fe_store(o + 2 * NW, zo);
+    } else {
+      fe_mask_select<C>(yv, inf, zero, yv);
+      u32* o = out + i * 2 * NW;
+      C::fe_store(o, x); C::fe_store(o + NW, yv);
+      if (out_inf) out_inf[i] = (uint8_t)(inf & 1u);
+    }
+  }
+}
+
 // One pass of one lane: units base, base + T, .., base + (BATCH - 1) T (those below n).
 template <class C, int BATCH>
 ECGPU_HD void lane_pass(const u32* scalars, const u32* points, int pt_fmt, u32* out, int out_fmt, uint8_t* out_inf, size_t n, size_t base,
@@ -157,32 +281,8 @@ ECGPU_HD void lane_pass(const u32* scalars, const u32* points, int pt_fmt, u32* 
     const size_t i = base + (size_t)s * T;
     if (i >= n) break;                         // public: the batch size
     cnt = s + 1;
-    const u32* src = points + i * pw;
     Jac<C> p;
-    C::fe_load(p.x, src);
-    C::fe_load(p.y, src + NW);
-    u32 inf_mask;
-    if (pt_fmt == FMT_PROJECTIVE) {            // public: the wire format
-      C::fe_load(p.z, src + 2 * NW);
-      inf_mask = fe_zero_mask<C>(p.z);
-      Fe zz;
-      C::fe_mul(p.x, p.x, p.z);                // homogeneous (X : Y : Z) is Jacobian (X Z : Y Z^2 : Z)
-      C::fe_sqr(zz, p.z);
-      C::fe_mul(p.y, p.y, zz);
-    } else {
-      u32 z = 0;
-#pragma unroll
-      for (int w = 0; w < 2 * NW; w++) z |= src[w];
-      inf_mask = 0u - (((z | (0u - z)) >> 31) ^ 1u);
-      p.z = one;
-    }
-    {                                          // an identity input: keep the arithmetic on a valid point (G), force the result later
-      typename C::Pt g;
-      C::pt_generator(g);
-      fe_mask_select<C>(p.x, inf_mask, g.x, p.x);
-      fe_mask_select<C>(p.y, inf_mask, g.y, p.y);
-      fe_mask_select<C>(p.z, inf_mask, one, p.z);
-    }
+    const u32 inf_mask = load_point<C>(p.x, p.y, p.z, points + i * pw, pt_fmt, one);
     infs |= (inf_mask & 1u) << s;
     // co-Z chain (jacobian.hpp): 2P with P rewritten to its denominator, then (e + 1) P = e P + P, every step rewriting P again.
     // Entry e holds (x, y) of (e + 1) P over the denominator D_e; its z slot the ratio D_e / D_(e-1) (entries 2 .. 7);
@@ -256,7 +356,7 @@ ECGPU_HD void lane_pass(const u32* scalars, const u32* points, int pt_fmt, u32* 
     for (int w = 0; w < NW; w++) dm.st(w, addc(k[w], 0x88888888u, c));       // the recoded digits leave the registers (DigitMem)
     Jac<C> acc;
     jac::set_infinity<C>(acc);
-    u32 acc_inf = 0xFFFFFFFFu;                 // mask: the accumulator is still empty
+    u32 empty = 0xFFFFFFFFu;                   // mask: the accumulator is still empty
 #pragma unroll 1
     for (int j = 8 * NW; j >= 0; j--) {         // position 8 NW holds the carry digit (0 or 1)
       if (j != 8 * NW) {
@@ -266,13 +366,12 @@ ECGPU_HD void lane_pass(const u32* scalars, const u32* points, int pt_fmt, u32* 
       const u32 word = dm.ld(j == 8 * NW ? 0 : (j >> 3));                       // the address is public (the loop counter)
       const u32 nib = (word >> (4 * (j & 7))) & 15u;
       const int sd = (j == 8 * NW) ? (int)c : (int)nib - 8;
-      const u32 sgn = (u32)(sd >> 31), mag = ((u32)sd ^ sgn) - sgn;               // |digit| in 0..8
-      const u32 zero_digit = 0u - ((mag - 1u) >> 31);
+      const SignMag dg = sign_mag(sd);                                            // |digit| in 0..8
       Fe qx = zero, qy = zero;
 #pragma unroll 2
       for (int e = 0; e < 8; e++) {
         ECGPU_TABLE_TOUCH(b * 8 + e);
-        const u32 mk = 0u - (((mag ^ (u32)(e + 1)) - 1u) >> 31);                  // all ones iff mag == e + 1
+        const u32 mk = mask_eq(dg.mag, (u32)(e + 1));
         Fe tx, ty;
         fe_ld<C>(tx, ws, entry_chunk<C>(0, 0) + (b * 8 + e) * 3 * CW);
         fe_ld<C>(ty, ws, entry_chunk<C>(0, 0) + (b * 8 + e) * 3 * CW + CW);
@@ -281,76 +380,20 @@ ECGPU_HD void lane_pass(const u32* scalars, const u32* points, int pt_fmt, u32* 
       }
       Fe ny;
       C::fe_neg(ny, qy);
-      fe_mask_select<C>(qy, sgn ^ flip, ny, qy);       // digit < 0 xor scalar folded: subtract the entry
-      Jac<C> s = acc;
-      add_mixed_raw<C>(s, qx, qy);
+      fe_mask_select<C>(qy, dg.sgn ^ flip, ny, qy);    // digit < 0 xor scalar folded: subtract the entry
       // empty accumulator: the sum is the entry itself; zero digit: the accumulator stays
-      fe_mask_select<C>(s.x, acc_inf, qx, s.x);
-      fe_mask_select<C>(s.y, acc_inf, qy, s.y);
-      fe_mask_select<C>(s.z, acc_inf, one, s.z);
-      fe_mask_select<C>(acc.x, zero_digit, acc.x, s.x);
-      fe_mask_select<C>(acc.y, zero_digit, acc.y, s.y);
-      fe_mask_select<C>(acc.z, zero_digit, acc.z, s.z);
-      acc_inf &= zero_digit;
+      ct_accumulate<C>(acc, empty, qx, qy, mask_eq(dg.mag, 0u), one);
     }
-    const u32 inf = acc_inf | (0u - ((infs >> b) & 1u));
+    const u32 inf = empty | mask_bit(infs, b);
     res_inf |= (inf & 1u) << b;
     fe_mask_select<C>(acc.z, inf, one, acc.z);          // keep the shared inversion clean
     jac_st<C>(ws, entry_chunk<C>(b, 0), acc);
   }
 #pragma unroll
   for (int w = 0; w < NW; w++) dm.st(w, 0u);            // the last unit's recoded scalar does not stay in LDS
-  // ---- phase D: x = X / Z^2, y = Y / Z^3 with one inversion for the cnt results of this lane
-  {
-    Fe run = one;
-#pragma unroll 1
-    for (int b = 0; b < cnt; b++) {
-      Fe z;
-      fe_st<C>(ws, pre_chunk<C, BATCH>(b), run);
-      fe_ld<C>(z, ws, entry_chunk<C>(b, 0) + 2 * CW);
-      // Z = 0 besides the tracked identities: only for input that is not on the curve (a small-order point of another cubic makes the raw
-      // addition meet acc = +-Q).  It must not reach the shared product: fe_inv(0) = 0 would wipe every result of this lane's pass.
-      const u32 zm = fe_zero_mask<C>(z) | (0u - ((res_inf >> b) & 1u));
-      res_inf |= (zm & 1u) << b;
-      fe_mask_select<C>(z, zm, one, z);
-      C::fe_mul(run, run, z);
-    }
-    Fe inv;
-    C::fe_inv(inv, run);
-#pragma unroll 1
-    for (int b = cnt - 1; b >= 0; b--) {
-      const size_t i = base + (size_t)b * T;
-      const u32 inf = 0u - ((res_inf >> b) & 1u);
-      Fe z, pre, zi, t, x, yv;
-      fe_ld<C>(z, ws, entry_chunk<C>(b, 0) + 2 * CW);
-      fe_mask_select<C>(z, inf, one, z);
-      fe_ld<C>(pre, ws, pre_chunk<C, BATCH>(b));
-      C::fe_mul(zi, inv, pre);
-      C::fe_mul(inv, inv, z);
-      C::fe_sqr(t, zi);
-      fe_ld<C>(x, ws, entry_chunk<C>(b, 0));
-      C::fe_mul(x, x, t);
-      C::fe_mul(t, t, zi);
-      fe_ld<C>(yv, ws, entry_chunk<C>(b, 0) + CW);
-      C::fe_mul(yv, yv, t);
-      // the parked result and its prefix product are secrets of the same rank as the output: they do not stay in the workspace
-      fe_st<C>(ws, entry_chunk<C>(b, 0), zero); fe_st<C>(ws, entry_chunk<C>(b, 0) + CW, zero); fe_st<C>(ws, entry_chunk<C>(b, 0) + 2 * CW, zero);
-      fe_st<C>(ws, pre_chunk<C, BATCH>(b), zero);
-      fe_mask_select<C>(x, inf, zero, x);
-      if (out_fmt == FMT_PROJECTIVE) {          // public: the wire format.  (x : y : 1), identity (0 : 1 : 0)
-        Fe zo;
-        fe_mask_select<C>(yv, inf, one, yv);
-        fe_mask_select<C>(zo, inf, zero, one);
-        u32* o = out + i * 3 * NW;
-        C::fe_store(o, x); C::fe_store(o + NW, yv); C::fe_store(o + 2 * NW, zo);
-      } else {
-        fe_mask_select<C>(yv, inf, zero, yv);
-        u32* o = out + i * 2 * NW;
-        C::fe_store(o, x); C::fe_store(o + NW, yv);
-        if (out_inf) out_inf[i] = (uint8_t)(inf & 1u);
-      }
-    }
-  }
+  // ---- phase D: the results leave their table slots
+  store_results<C>(out, out_fmt, out_inf, base, T, ws, cnt, res_inf, [](int b) { return entry_chunk<C>(b, 0); },
+                   [](int b) { return pre_chunk<C, BATCH>(b); });
 }
 
 }  // namespace vbct

@@ -48,19 +48,15 @@ namespace ecgpu {
 namespace vbct {
 
 // all ones iff the weakly reduced field element is zero (raw 0 or raw p), arithmetic
-ECGPU_HD u32 k256_zero_mask(const FeK256& a) {
+template <>
+ECGPU_HD u32 fe_zero_mask<CurveK256>(const FeK256& a) {
   u32 z = 0, o = 0xFFFFFFFFu;
 #pragma unroll
   for (int w = 0; w < 8; w++) z |= a.v[w];
 #pragma unroll
   for (int w = 2; w < 8; w++) o &= a.v[w];
   const u32 np = ~o | (a.v[1] ^ 0xFFFFFFFEu) | (a.v[0] ^ (0u - k256::C_LO));     // zero iff a is the raw modulus
-  const u32 is0 = ((z | (0u - z)) >> 31) ^ 1u, isp = ((np | (0u - np)) >> 31) ^ 1u;
-  return 0u - (is0 | isp);
-}
-ECGPU_HD void k256_mask_select(FeK256& r, u32 mk, const FeK256& a, const FeK256& b) {
-#pragma unroll
-  for (int w = 0; w < 8; w++) r.v[w] = (a.v[w] & mk) | (b.v[w] & ~mk);
+  return mask_zero(z) | mask_zero(np);
 }
 
 // p += (x2, y2) by the plain Jacobian mixed addition (8M + 3S), NO exceptional-case handling: valid iff p is finite and
@@ -85,19 +81,12 @@ ECGPU_HD void k256_add_mixed_raw(JacK256& p, const FeK256& x2, const FeK256& y2,
   mul_add2(p.y, r, t, u, h);                 // Y3 = R (V - X3) + (-Y1) HHH, one reduction (fe_k256.hpp)
 }
 
-// acc += (qx, qy) for every digit; `zd` is all ones iff the digit is zero (acc is kept), `empty` all ones while acc is still O
-// (the result is then the entry itself).  Both are masks; the addition itself always executes.
+// acc += (qx, qy) for every digit, resolved by masks: the secp256k1 form of vbct::ct_accumulate (varbase_ct.hpp), on this curve's
+// accumulator and raw addition
 ECGPU_HD void k256_ct_accumulate(JacK256& acc, u32& empty, const FeK256& qx, const FeK256& qy, u32 zd, const FeK256& one) {
   JacK256 t = acc;
-  k256_add_mixed_raw(t, qx, qy, nullptr);                                            // garbage for an empty accumulator or a zero digit
-  const u32 take_q = empty & ~zd;                                                    // first non-zero digit
-  k256_mask_select(t.x, take_q, qx, t.x);
-  k256_mask_select(t.y, take_q, qy, t.y);
-  k256_mask_select(t.z, take_q, one, t.z);
-  k256_mask_select(acc.x, zd, acc.x, t.x);
-  k256_mask_select(acc.y, zd, acc.y, t.y);
-  k256_mask_select(acc.z, zd, acc.z, t.z);
-  empty &= zd;
+  k256_add_mixed_raw(t, qx, qy, nullptr);
+  ct_resolve<CurveK256>(acc, t, empty, qx, qy, zd, one);
 }
 
 // chunk layout of one lane: the unit's table (8 entries x (x, y)), the H ratios of its construction (zr[2 .. 7]), then per slot
@@ -124,33 +113,10 @@ ECGPU_HD void lane_pass_k256(const u32* scalars, const u32* points, int pt_fmt, 
     const size_t i = base + (size_t)b * T;
     if (i >= n) break;                         // public: the batch size
     cnt = b + 1;
-    // ---- the point (public data; identity inputs are replaced by G under a mask and the result forced to the identity)
-    const u32* src = points + i * pw;
+    // ---- the point (public data; identity inputs are replaced by G under a mask and the result forced to the identity).
+    //      Homogeneous input comes as Jacobian (XZ, YZ^2, Z): the loop runs on the curve isomorphic by u = Z
     FeK256 px, py, pz;
-    C::fe_load(px, src);
-    C::fe_load(py, src + NW);
-    u32 inf_mask;
-    if (pt_fmt == FMT_PROJECTIVE) {            // public: the wire format.  Homogeneous (X : Y : Z) = Jacobian (XZ, YZ^2, Z): run on the curve isomorphic by u = Z
-      C::fe_load(pz, src + 2 * NW);
-      inf_mask = k256_zero_mask(pz);
-      FeK256 zz;
-      k256::mul(px, px, pz);
-      k256::sqr(zz, pz);
-      k256::mul(py, py, zz);
-    } else {
-      u32 z = 0;
-#pragma unroll
-      for (int w = 0; w < 2 * NW; w++) z |= src[w];
-      inf_mask = 0u - (((z | (0u - z)) >> 31) ^ 1u);
-      pz = one;
-    }
-    {
-      PtK256 g;
-      k256::generator(g);
-      k256_mask_select(px, inf_mask, g.x, px);
-      k256_mask_select(py, inf_mask, g.y, py);
-      k256_mask_select(pz, inf_mask, one, pz);
-    }
+    const u32 inf_mask = load_point<C>(px, py, pz, points + i * pw, pt_fmt, one);
     // ---- the unit's table [P .. 8P] with the common denominator Z8 (mulfast_k256.hpp::table_build_globalz, branch-free and
     //      through the workspace): the co-Z chain 2P, 3P = 2P + P, .. rewrites P to the denominator of every new multiple, so
     //      each step is a co-Z addition (4M + 2S, no Z multiplied out; exception-free: (j -+ 1) P = O is impossible), the ratios
@@ -212,14 +178,12 @@ ECGPU_HD void lane_pass_k256(const u32* scalars, const u32* points, int pt_fmt, 
       const u32 w1 = dm.ld(j == 32 ? 0 : (j >> 3)), w2 = dm.ld(4 + (j == 32 ? 0 : (j >> 3)));
       const int s1 = (j == 32) ? (int)d1.top : k256::radix16_digit(w1, j & 7);
       const int s2 = (j == 32) ? (int)d2.top : k256::radix16_digit(w2, j & 7);
-      const u32 sg1 = (u32)(s1 >> 31), sg2 = (u32)(s2 >> 31);
-      const u32 mag1 = ((u32)s1 ^ sg1) - sg1, mag2 = ((u32)s2 ^ sg2) - sg2;           // 0 .. 8
+      const SignMag g1 = sign_mag(s1), g2 = sign_mag(s2);                             // magnitudes 0 .. 8
       FeK256 q1x = zero, q1y = zero, q2x = zero, q2y = zero;
 #pragma unroll 2
       for (int e = 0; e < 8; e++) {
         ECGPU_TABLE_TOUCH(b * 8 + e);
-        const u32 m1 = 0u - (((mag1 ^ (u32)(e + 1)) - 1u) >> 31);                    // all ones iff mag1 == e + 1
-        const u32 m2 = 0u - (((mag2 ^ (u32)(e + 1)) - 1u) >> 31);
+        const u32 m1 = mask_eq(g1.mag, (u32)(e + 1)), m2 = mask_eq(g2.mag, (u32)(e + 1));
         FeK256 tx, ty;
         fe_ld<C>(tx, ws, K256_CT_TAB + 4 * e);
         fe_ld<C>(ty, ws, K256_CT_TAB + 4 * e + CW);
@@ -232,11 +196,11 @@ ECGPU_HD void lane_pass_k256(const u32* scalars, const u32* points, int pt_fmt, 
       k256::mul(q2x, q2x, beta_);                                                    // lambda (x, y) = (beta x, y)
       FeK256 ny;
       k256::neg(ny, q1y);
-      k256_mask_select(q1y, sg1 ^ neg1, ny, q1y);                                    // digit < 0 xor half negative
+      fe_mask_select<C>(q1y, g1.sgn ^ neg1, ny, q1y);                                 // digit < 0 xor half negative
       k256::neg(ny, q2y);
-      k256_mask_select(q2y, sg2 ^ neg2, ny, q2y);
-      k256_ct_accumulate(acc, empty, q1x, q1y, 0u - ((mag1 - 1u) >> 31), one);
-      k256_ct_accumulate(acc, empty, q2x, q2y, 0u - ((mag2 - 1u) >> 31), one);
+      fe_mask_select<C>(q2y, g2.sgn ^ neg2, ny, q2y);
+      k256_ct_accumulate(acc, empty, q1x, q1y, mask_eq(g1.mag, 0u), one);
+      k256_ct_accumulate(acc, empty, q2x, q2y, mask_eq(g2.mag, 0u), one);
     }
     k256::mul(acc.z, acc.z, zfix);
     const u32 inf = inf_mask | empty;                     // an identity input or k = 0 mod n: the identity
@@ -245,55 +209,9 @@ ECGPU_HD void lane_pass_k256(const u32* scalars, const u32* points, int pt_fmt, 
   }
 #pragma unroll
   for (int w = 0; w < 8; w++) dm.st(w, 0u);             // the last unit's recoded halves do not stay in LDS
-  // ---- x = X / Z^2, y = Y / Z^3 with one inversion for the cnt results of this lane
-  {
-    FeK256 run = one;
-#pragma unroll 1
-    for (int b = 0; b < cnt; b++) {
-      FeK256 z;
-      fe_st<C>(ws, k256_pre_chunk<BATCH>(b), run);
-      fe_ld<C>(z, ws, k256_res_chunk<BATCH>(b) + 2 * CW);
-      const u32 zm = k256_zero_mask(z) | (0u - ((res_inf >> b) & 1u));     // Z = 0 besides the identity: only for input that is not on the curve
-      res_inf |= (zm & 1u) << b;
-      k256_mask_select(z, zm, one, z);
-      k256::mul(run, run, z);
-    }
-    FeK256 inv;
-    k256::inv(inv, run);
-#pragma unroll 1
-    for (int b = cnt - 1; b >= 0; b--) {
-      const size_t i = base + (size_t)b * T;
-      const u32 inf = 0u - ((res_inf >> b) & 1u);
-      FeK256 z, pre, zi, zi2, zi3, x, yv;
-      fe_ld<C>(z, ws, k256_res_chunk<BATCH>(b) + 2 * CW);
-      k256_mask_select(z, inf, one, z);
-      fe_ld<C>(pre, ws, k256_pre_chunk<BATCH>(b));
-      k256::mul(zi, inv, pre);
-      k256::mul(inv, inv, z);
-      k256::sqr(zi2, zi);
-      k256::mul(zi3, zi2, zi);
-      fe_ld<C>(x, ws, k256_res_chunk<BATCH>(b));
-      k256::mul(x, x, zi2);
-      fe_ld<C>(yv, ws, k256_res_chunk<BATCH>(b) + CW);
-      k256::mul(yv, yv, zi3);
-      // the parked result and its prefix product are secrets of the same rank as the output: they do not stay in the workspace
-      fe_st<C>(ws, k256_res_chunk<BATCH>(b), zero); fe_st<C>(ws, k256_res_chunk<BATCH>(b) + CW, zero); fe_st<C>(ws, k256_res_chunk<BATCH>(b) + 2 * CW, zero);
-      fe_st<C>(ws, k256_pre_chunk<BATCH>(b), zero);
-      k256_mask_select(x, inf, zero, x);
-      if (out_fmt == FMT_PROJECTIVE) {          // public: the wire format.  (x : y : 1), identity (0 : 1 : 0)
-        FeK256 zo;
-        k256_mask_select(yv, inf, one, yv);
-        k256_mask_select(zo, inf, zero, one);
-        u32* o = out + i * 3 * NW;
-        C::fe_store(o, x); C::fe_store(o + NW, yv); C::fe_store(o + 2 * NW, zo);
-      } else {
-        k256_mask_select(yv, inf, zero, yv);
-        u32* o = out + i * 2 * NW;
-        C::fe_store(o, x); C::fe_store(o + NW, yv);
-        if (out_inf) out_inf[i] = (uint8_t)(inf & 1u);
-      }
-    }
-  }
+  // ---- per-lane batched conversion of the parked results to affine, identity results by masks
+  store_results<C>(out, out_fmt, out_inf, base, T, ws, cnt, res_inf, [](int b) { return k256_res_chunk<BATCH>(b); },
+                   [](int b) { return k256_pre_chunk<BATCH>(b); });
 }
 
 }  // namespace vbct

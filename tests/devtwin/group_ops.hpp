@@ -1,5 +1,6 @@
 // TEST-ONLY op table over the point formulas (csrc/jacobian.hpp, msm.hpp, mulfast_k256.hpp) and the masked additions of the
-// constant-time kernels (varbase_ct_k256.hpp, varbase_ct.hpp, fixedbase_ct.hpp), one pair of operands per call.  The same
+// constant-time kernels (varbase_ct_k256.hpp, varbase_ct.hpp, fixedbase_ct.hpp: the very functions their window loops call), one
+// pair of operands per call.  The same
 // functions are compiled for gfx950 into tests/devtwin (devtwin_group.hip: one pair per lane, so a wave's lanes can disagree
 // about the branch they take) and for the host into tests/hosttwin (hosttwin_group.cpp: the ECGPU_EXC_NOTE counters say which
 // branch a vector reached).  Operands and results are the field's internal words, raw and little-endian, with no conversion
@@ -32,10 +33,11 @@ enum PtOp {
   G_XYZZ_ADD_AFFINE,     // msm::xyzz_add_affine((p.X, p.Y, 1, 1), q affine)
   G_XYZZ_ADD,            // msm::xyzz_add(p, q)
   G_XYZZ_ROUNDTRIP,      // jacobian_to_xyzz(p) then xyzz_to_jacobian: the triple in 0..2, the ZZZ in between in 3
-  // the masked addition of fixedbase_ct.hpp (mul_ct_one): fb::xyzz_add_mixed_raw and its selects.  flag: `empty` afterwards
+  // the masked addition that fb::mul_ct_one calls for every digit: fb::xyzz_ct_accumulate(p, empty, q affine, |digit|, one).
+  // flag: `empty` afterwards
   M_FB_ACCUMULATE,
-  // the masked addition of varbase_ct.hpp (P-256 / P-384: fully reduced fields): vbct::add_mixed_raw and its selects.
-  // flag bit 0: `empty` afterwards, bit 1: fe_zero_mask of the resulting Z
+  // the masked addition that vbct::lane_pass calls for every digit (P-256 / P-384: fully reduced fields):
+  // vbct::ct_accumulate(p, empty, q affine, zd, one).  flag bit 0: `empty` afterwards, bit 1: fe_zero_mask of the resulting Z
   M_VBCT_ACCUMULATE,
   // secp256k1 only
   K_JAC_ADD_MIXED,       // k256::jac_add_mixed(p, q affine, &zr): zr in element 4
@@ -118,22 +120,13 @@ ECGPU_HD bool pt_op(int op, const u32* p, const u32* q, const u32* aux, u32* out
         msm::xyzz_to_jacobian<C>(a, t);
         break;
       }
-      default:                                   // M_VBCT_ACCUMULATE: the window loop's addition (varbase_ct.hpp, lane_pass phase C)
+      default:                                   // M_VBCT_ACCUMULATE
         if constexpr (!C::A_IS_ZERO) {
           Fe one;
           C::fe_one(one);
-          u32 acc_inf = aux[0];
-          const u32 zero_digit = aux[1];
-          Jac<C> s = a;
-          vbct::add_mixed_raw<C>(s, qi[0], qi[1]);
-          vbct::fe_mask_select<C>(s.x, acc_inf, qi[0], s.x);
-          vbct::fe_mask_select<C>(s.y, acc_inf, qi[1], s.y);
-          vbct::fe_mask_select<C>(s.z, acc_inf, one, s.z);
-          vbct::fe_mask_select<C>(a.x, zero_digit, a.x, s.x);
-          vbct::fe_mask_select<C>(a.y, zero_digit, a.y, s.y);
-          vbct::fe_mask_select<C>(a.z, zero_digit, a.z, s.z);
-          acc_inf &= zero_digit;
-          flag = (acc_inf & 1u) | (vbct::fe_zero_mask<C>(a.z) & 2u);
+          u32 empty = aux[0];
+          vbct::ct_accumulate<C>(a, empty, qi[0], qi[1], aux[1], one);
+          flag = (empty & 1u) | (vbct::fe_zero_mask<C>(a.z) & 2u);
         } else {
           ok = false;
         }
@@ -147,23 +140,11 @@ ECGPU_HD bool pt_op(int op, const u32* p, const u32* q, const u32* aux, u32* out
       case G_XYZZ_ADD_MIXED: msm::xyzz_add_mixed<C>(a, qi[0], qi[1]); break;
       case G_XYZZ_ADD_AFFINE: C::fe_one(a.zz); C::fe_one(a.zzz); msm::xyzz_add_affine<C>(a, qi[0], qi[1]); break;
       case G_XYZZ_ADD: msm::xyzz_add<C>(a, b); break;
-      case M_FB_ACCUMULATE: {                    // the window loop's addition (fixedbase_ct.hpp, mul_ct_one)
+      case M_FB_ACCUMULATE: {                    // aux[1] is the zero-digit mask: magnitude 0 for a zero digit, 1 for any other
         Fe one;
         C::fe_one(one);
         u32 empty = aux[0];
-        const u32 zd = aux[1];
-        msm::Xyzz<C> t = a;
-        fb::xyzz_add_mixed_raw<C>(t, qi[0], qi[1]);
-        const u32 take_q = empty & ~zd;
-        vbct::fe_mask_select<C>(t.x, take_q, qi[0], t.x);
-        vbct::fe_mask_select<C>(t.y, take_q, qi[1], t.y);
-        vbct::fe_mask_select<C>(t.zz, take_q, one, t.zz);
-        vbct::fe_mask_select<C>(t.zzz, take_q, one, t.zzz);
-        vbct::fe_mask_select<C>(a.x, zd, a.x, t.x);
-        vbct::fe_mask_select<C>(a.y, zd, a.y, t.y);
-        vbct::fe_mask_select<C>(a.zz, zd, a.zz, t.zz);
-        vbct::fe_mask_select<C>(a.zzz, zd, a.zzz, t.zzz);
-        empty &= zd;
+        fb::xyzz_ct_accumulate<C>(a, empty, qi[0], qi[1], ~aux[1] & 1u, one);
         flag = empty;
         break;
       }
