@@ -503,10 +503,7 @@ struct CurveOps {
     if (rc) return rc;
     // the products are secrets of the same rank as the shared values handed back: they do not stay in the workspace, whichever way
     // this function is left (the constant-time kernels clear what they park in the table workspace themselves)
-    struct ProdWipe {
-      ecgpu_ctx* c; void* p; size_t b;
-      ~ProdWipe() { (void)hipMemsetAsync(p, 0, b, c->stream); }
-    } prod_wipe{c, prod, n * 2 * C::NB};
+    StreamWipe prod_wipe{c, prod, n * 2 * C::NB};
     hipLaunchKernelGGL((ecdh::prep_kernel<C>), dim3(ecgpu_grid_for(c, n, 8)), dim3(256), 0, c->stream, d, q, q_sane, ok, n);
     HIPCHK(c, hipGetLastError());
     if ((rc = lincomb(c, d, q_sane, FMT_AFFINE, 1, prod, FMT_AFFINE, nullptr, n, (unsigned)ECGPU_SECRET_SCALARS))) return rc;
@@ -540,10 +537,6 @@ struct CurveOps {
   }
   // Deterministic signing (signing_kernels.hpp).  The derived nonces pass through the intermediate workspace and are secrets of the
   // key's rank: they are cleared on the stream whichever way the launcher is left (the fixed-base kernels keep nothing of a scalar).
-  struct NonceWipe {
-    ecgpu_ctx* c; void* p; size_t b;
-    ~NonceWipe() { (void)hipMemsetAsync(p, 0, b, c->stream); }
-  };
   static int rfc6979_nonce(ecgpu_ctx* c, const u32* d, const u32* z, const u32* extra, u32* k, size_t n) {
     const unsigned g = ecgpu_grid_for(c, n, 8);
     if (extra) hipLaunchKernelGGL((sign::rfc6979_nonce_kernel<C, true>), dim3(g), dim3(256), 0, c->stream, d, z, extra, k, n);
@@ -560,7 +553,7 @@ struct CurveOps {
       k = ws.take<u32>(n * C::NB);
     });
     if (rc) return rc;
-    NonceWipe wipe{c, k, n * C::NB};
+    StreamWipe wipe{c, k, n * C::NB};
     if ((rc = rfc6979_nonce(c, d, z, extra, k, n))) return rc;
     return ecdsa_sign_body(c, d, k, z, r_xy, r_inf, sig, recid, ok, n, flags);
   }
@@ -572,7 +565,7 @@ struct CurveOps {
       u32 *p_xy, *r_xy, *k;
       int rc = ecgpu_carve(c, c->ecdsa_ws, [&](WsCarver& ws) { p_xy = ws.take<u32>(n * 2 * C::NB); r_xy = ws.take<u32>(n * 2 * C::NB); k = ws.take<u32>(n * C::NB); });
       if (rc) return rc;
-      NonceWipe wipe{c, k, n * C::NB};
+      StreamWipe wipe{c, k, n * C::NB};
       const unsigned g = ecgpu_grid_for(c, n, 8);
       if ((rc = mul_gen_ct(c, d, p_xy, FMT_AFFINE, nullptr, n))) return rc;
       hipLaunchKernelGGL((sign::schnorr_nonce_kernel<0>), dim3(g), dim3(256), 0, c->stream, d, (const u32*)p_xy, aux, m, k, n);

@@ -11,6 +11,7 @@
 //   sign:    fixed-base kernel (k G) -> sign_finish (r, batched k^-1, s, recovery id)
 // Device code only.
 #pragma once
+#include "affine_ops.hpp"
 #include "kernels.hpp"
 #include "scalar_mont.hpp"
 
@@ -51,19 +52,15 @@ __device__ __forceinline__ bool is_high(const u32* x) {      // x > (n - 1) / 2 
 template <class C>
 __device__ __forceinline__ bool public_key_ok(const u32* xy) {
   constexpr int NW = C::NW;
-  u32 lx[NW], ly[NW], p[NW];
-  words_load_be<NW>(lx, xy);
-  words_load_be<NW>(ly, xy + NW);
-  C::modulus(p);
-  if (mp_geq<NW>(lx, p) || mp_geq<NW>(ly, p)) return false;
-  if (mp_is_zero<NW>(lx) && mp_is_zero<NW>(ly)) return false;
-  typename C::Fe x, y, l, r, d;
+  if (!aff::coords_canonical<C>(xy, xy + NW)) return false;
+  u32 z = 0;
+#pragma unroll
+  for (int j = 0; j < 2 * NW; j++) z |= xy[j];
+  if (z == 0) return false;
+  typename C::Fe x, y;
   C::fe_load(x, xy);
   C::fe_load(y, xy + NW);
-  C::fe_sqr(l, y);
-  C::curve_rhs(r, x);
-  C::fe_sub(d, l, r);
-  return C::fe_is_zero(d);
+  return aff::on_curve<C>(x, y);
 }
 
 // Batched inversion of BATCH scalars held in Montgomery form (Montgomery's trick), in place.
@@ -157,53 +154,34 @@ __global__ void __launch_bounds__(256) verify_check_kernel(const u32* a_xy, cons
     const u32* pa = a_xy + i * 2 * L;
     const u32* pb = b_xy + i * 2 * L;
     bool valid = false;
-    if (ai && bi) {
-      valid = false;
-    } else if (ai || bi) {
+    const u32 kind = aff::sum_kind<C>(pa, ai, pb, bi);
+    if (kind == aff::SUM_OPERAND) {
       u32 x[L];
       ecdsa::load_be<L>(x, (ai ? pb : pa));
       valid = mp_eq<L>(x, r) || (second && mp_eq<L>(x, r2));
-    } else {
-      Fe xa, ya, xb, yb, N, D, t, lhs, s;
+    } else if (kind & aff::SUM_CHORD) {
+      Fe xa, ya, xb, yb, N, D, lhs, s;
       C::fe_load(xa, pa); C::fe_load(ya, pa + L);
       C::fe_load(xb, pb); C::fe_load(yb, pb + L);
-      bool same_x = true, same_y = true;
-#pragma unroll
-      for (int j = 0; j < L; j++) { same_x &= (pa[j] == pb[j]); same_y &= (pa[L + j] == pb[L + j]); }
-      bool defined = true;
-      if (same_x) {
-        if (same_y) {                 // tangent: N = 3 x^2 + a, D = 2 y  (y != 0 on a curve of odd order)
-          C::fe_sqr(t, xa);
-          if (!C::A_IS_ZERO) { Fe one; C::fe_one(one); C::fe_sub(t, t, one); }
-          C::fe_add(N, t, t); C::fe_add(N, N, t);
-          C::fe_add(D, ya, ya);
-        } else {
-          defined = false;            // A = -B: the sum is the identity
-        }
-      } else {
-        C::fe_sub(N, yb, ya);
-        C::fe_sub(D, xb, xa);
-      }
-      if (defined) {
-        C::fe_sqr(lhs, N);
-        C::fe_sqr(D, D);
-        C::fe_add(s, xa, xb);
-        u32 be[L];
-        Fe c, rhs, d;
-        ecdsa::store_be<L>(be, r);
+      aff::slope_terms<C>(N, D, xa, ya, xb, yb, kind == aff::SUM_TANGENT);
+      C::fe_sqr(lhs, N);
+      C::fe_sqr(D, D);
+      C::fe_add(s, xa, xb);
+      u32 be[L];
+      Fe c, rhs, d;
+      ecdsa::store_be<L>(be, r);
+      C::fe_load(c, be);
+      C::fe_add(c, c, s);
+      C::fe_mul(rhs, c, D);
+      C::fe_sub(d, lhs, rhs);
+      valid = C::fe_is_zero(d);
+      if (!valid && second) {
+        ecdsa::store_be<L>(be, r2);
         C::fe_load(c, be);
         C::fe_add(c, c, s);
         C::fe_mul(rhs, c, D);
         C::fe_sub(d, lhs, rhs);
         valid = C::fe_is_zero(d);
-        if (!valid && second) {
-          ecdsa::store_be<L>(be, r2);
-          C::fe_load(c, be);
-          C::fe_add(c, c, s);
-          C::fe_mul(rhs, c, D);
-          C::fe_sub(d, lhs, rhs);
-          valid = C::fe_is_zero(d);
-        }
       }
     }
     ok[i] = valid ? 1 : 0;
@@ -304,13 +282,9 @@ __global__ void __launch_bounds__(256) recover_prep_kernel(const u32* z, const u
       }
       u32 xb[L];
       store_be<L>(xb, x);
-      Fe fx, rhs, y, ny;
+      Fe fx, y;
       C::fe_load(fx, xb);
-      C::curve_rhs(rhs, fx);
-      const bool has = C::fe_sqrt(y, rhs);
-      C::fe_neg(ny, y);
-      const bool odd = C::fe_is_odd(y);
-      C::fe_select(y, odd == ((recid[i] & 1) != 0), y, ny);
+      const bool has = aff::lift_x<C>(y, fx, (recid[i] & 1) != 0);
       g = g && has;
       if (!g) { C::fe_zero(fx); C::fe_zero(y); mp_zero<L>(r); r[0] = 1; }
       C::fe_store(r_xy + i * 2 * L, fx);
@@ -346,78 +320,14 @@ __global__ void __launch_bounds__(256) recover_finish_kernel(const u32* a_xy, co
                                                              uint8_t* ok, size_t n) {
   using Fe = typename C::Fe;
   constexpr int L = C::NW;
-  Fe pre[BATCH];
   const size_t T = (size_t)gridDim.x * blockDim.x;
   const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   for (size_t base = tid; base < n; base += T * BATCH) {
-    u32 kinds = 0;          // 0 = identity / rejected, 1 = one operand is the identity, 2 = chord or tangent
-    int cnt = 0;
-    Fe acc; C::fe_one(acc);
-#pragma unroll 1
-    for (int b = 0; b < BATCH; b++) {
-      const size_t i = base + (size_t)b * T;
-      if (i >= n) break;
-      cnt = b + 1;
-      pre[b] = acc;
-      if (!ok[i]) continue;
-      const bool ai = a_inf[i] != 0, bi = b_inf[i] != 0;
-      if (ai && bi) continue;
-      if (ai || bi) { kinds |= 1u << (2 * b); continue; }
-      const u32* pa = a_xy + i * 2 * L;
-      const u32* pb = b_xy + i * 2 * L;
-      bool same_x = true, same_y = true;
-#pragma unroll
-      for (int j = 0; j < L; j++) { same_x &= (pa[j] == pb[j]); same_y &= (pa[L + j] == pb[L + j]); }
-      if (same_x && !same_y) continue;
-      Fe d, t;
-      if (same_x) { C::fe_load(t, pa + L); C::fe_add(d, t, t); }
-      else { Fe xa, xb; C::fe_load(xa, pa); C::fe_load(xb, pb); C::fe_sub(d, xb, xa); }
-      kinds |= 2u << (2 * b);
-      C::fe_mul(acc, acc, d);
-    }
-    Fe inv_all;
-    C::fe_inv(inv_all, acc);
-#pragma unroll 1
-    for (int b = cnt - 1; b >= 0; b--) {
-      const size_t i = base + (size_t)b * T;
-      const u32 kind = (kinds >> (2 * b)) & 3u;
-      const u32* pa = a_xy + i * 2 * L;
-      const u32* pb = b_xy + i * 2 * L;
-      Fe x3, y3;
-      C::fe_zero(x3); C::fe_zero(y3);
-      if (kind == 1) {
-        const u32* src = a_inf[i] ? pb : pa;
-        C::fe_load(x3, src);
-        C::fe_load(y3, src + L);
-      } else if (kind == 2) {
-        Fe xa, ya, xb, yb, N, D, di, lam, t;
-        C::fe_load(xa, pa); C::fe_load(ya, pa + L);
-        C::fe_load(xb, pb); C::fe_load(yb, pb + L);
-        bool same_x = true;
-#pragma unroll
-        for (int j = 0; j < L; j++) same_x &= (pa[j] == pb[j]);
-        if (same_x) {
-          C::fe_sqr(t, xa);
-          if (!C::A_IS_ZERO) { Fe one; C::fe_one(one); C::fe_sub(t, t, one); }
-          C::fe_add(N, t, t); C::fe_add(N, N, t);
-          C::fe_add(D, ya, ya);
-        } else {
-          C::fe_sub(N, yb, ya);
-          C::fe_sub(D, xb, xa);
-        }
-        C::fe_mul(di, inv_all, pre[b]);
-        C::fe_mul(inv_all, inv_all, D);
-        C::fe_mul(lam, N, di);
-        C::fe_sqr(x3, lam);
-        C::fe_sub(x3, x3, xa); C::fe_sub(x3, x3, xb);
-        C::fe_sub(t, xa, x3);
-        C::fe_mul(y3, lam, t);
-        C::fe_sub(y3, y3, ya);
-      }
+    aff::sum_batch<C, BATCH>(a_xy, a_inf, b_xy, b_inf, ok, base, T, n, [&](size_t i, u32 kind, const Fe& x3, const Fe& y3) {
       C::fe_store(out_xy + i * 2 * L, x3);
       C::fe_store(out_xy + i * 2 * L + L, y3);
       ok[i] = kind ? 1 : 0;
-    }
+    });
   }
 }
 

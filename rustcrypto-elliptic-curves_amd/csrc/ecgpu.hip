@@ -831,10 +831,7 @@ int ecgpu_hash_to_scalar_batch(ecgpu_ctx* c, int curve, const uint8_t* msgs, siz
     uint8_t* okm;
     int r = ecgpu_carve(c, c->ecdsa_ws, [&](WsCarver& ws) { okm = ws.take<uint8_t>(cnt * L); });
     if (r) return r;
-    struct OkmWipe {
-      ecgpu_ctx* c; void* p; size_t b;
-      ~OkmWipe() { (void)hipMemsetAsync(p, 0, b, c->stream); }
-    } okm_wipe{c, okm, cnt * L};
+    StreamWipe okm_wipe{c, okm, cnt * L};
     if ((r = ecgpuint_xmd(c, curve_hash(curve), (const uint8_t*)d[0], msg_stride, (const uint32_t*)d[1], tail, okm, cnt))) return r;
     return ops->scalar_reduce(c, okm, L, (uint32_t*)d[2], cnt, 0);
   });

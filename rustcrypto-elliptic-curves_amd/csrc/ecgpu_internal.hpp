@@ -131,6 +131,11 @@ static inline unsigned long long* ecgpu_sched_counter(ecgpu_ctx* c) {
   if (hipMemsetAsync(p, 0, sizeof(unsigned long long), c->stream) != hipSuccess) { ecgpu_set_err(c, ECGPU_ERR_RUNTIME, "hipMemsetAsync of a work counter failed"); return nullptr; }
   return p;
 }
+// Clears b bytes at p on the context's stream when the scope ends, whichever way a launcher is left: for secrets that pass through a workspace
+struct StreamWipe {
+  ecgpu_ctx* c; void* p; size_t b;
+  ~StreamWipe() { (void)hipMemsetAsync(p, 0, b, c->stream); }
+};
 static inline unsigned ecgpu_grid_for(const ecgpu_ctx* c, size_t n, int per_cu) {
   size_t blocks = (n + 255) / 256;
   size_t cap = (size_t)c->num_cus * per_cu;

@@ -7,6 +7,7 @@
 // DESIGN.md); what matters is VGPR pressure and instruction count.
 #pragma once
 #include "traits.hpp"
+#include "affine_ops.hpp"
 #include "mulfast_k256.hpp"
 #include "jacobian.hpp"
 #include "sched.hpp"
@@ -499,41 +500,25 @@ __global__ void __launch_bounds__(256) validate_points_kernel(const u32* xy, uin
     u32 z = 0;
 #pragma unroll
     for (int j = 0; j < 2 * C::NW; j++) { raw[j] = src[j]; z |= raw[j]; }
-    typename C::Fe x, y, l, r;
-    // canonical-range check must look at the raw integers, before any domain conversion
-    bool canon = true;
-    {
-      u32 lx[C::NW], ly[C::NW], p[C::NW];
-      words_load_be<C::NW>(lx, raw);
-      words_load_be<C::NW>(ly, raw + C::NW);
-      C::modulus(p);
-      canon = !mp_geq<C::NW>(lx, p) && !mp_geq<C::NW>(ly, p);
-    }
+    typename C::Fe x, y;
+    const bool canon = aff::coords_canonical<C>(raw, raw + C::NW);
     C::fe_load(x, raw);
     C::fe_load(y, raw + C::NW);
-    C::fe_sqr(l, y);
-    C::curve_rhs(r, x);
-    typename C::Fe d;
-    C::fe_sub(d, l, r);
-    ok[i] = (z == 0) || (canon && C::fe_is_zero(d)) ? 1 : 0;
+    ok[i] = (z == 0) || (canon && aff::on_curve<C>(x, y)) ? 1 : 0;
   }
 }
 template <class C>
 __global__ void __launch_bounds__(256) decompress_kernel(const u32* xs, const uint8_t* y_is_odd, u32* out_xy, uint8_t* ok, size_t n) {
   ECGPU_GRID_STRIDE(i, n) {
-    u32 raw[C::NW], lx[C::NW], p[C::NW];
+    u32 raw[C::NW];
 #pragma unroll
     for (int j = 0; j < C::NW; j++) raw[j] = xs[i * C::NW + j];
-    words_load_be<C::NW>(lx, raw);
-    C::modulus(p);
-    const bool canon = !mp_geq<C::NW>(lx, p);
-    typename C::Fe x, rhs, y, ny;
+    const bool canon = aff::coords_canonical<C>(raw);
+    typename C::Fe x, y, ny;
     C::fe_load(x, raw);
-    C::curve_rhs(rhs, x);
-    const bool has = C::fe_sqrt(y, rhs);
-    C::fe_neg(ny, y);
+    const bool has = aff::sqrt_rhs<C>(y, ny, x);
     const bool odd = C::fe_is_odd(y);
-    C::fe_select(y, odd == ((y_is_odd[i] & 1) != 0), y, ny);
+    C::fe_select(y, odd == ((y_is_odd[i] & 1) != 0), y, ny);      // the parity byte read here, after the root (aff::lift_x would hold it across the square root: one VGPR more on secp256k1)
     const bool good = canon && has;
     u32* o = out_xy + i * 2 * C::NW;
     typename C::Fe zero;
@@ -578,7 +563,7 @@ __global__ void __launch_bounds__(256) synth_scalars_kernel(u64 seed, u64 first,
 template <class C>
 __global__ void __launch_bounds__(256) synth_points_kernel(u64 seed, u64 first, u32* out_xy, size_t n) {
   ECGPU_GRID_STRIDE(i, n) {
-    typename C::Fe x, y, ny, rhs;
+    typename C::Fe x, y;
     bool found = false;
     for (int t = 0; t < 64 && !found; t++) {
       u32 v[C::NW], p[C::NW], be[C::NW];
@@ -588,13 +573,7 @@ __global__ void __launch_bounds__(256) synth_points_kernel(u64 seed, u64 first, 
       const u32 want_odd = (u32)synth_word(seed, 1 + t, first + i, 7) & 1u;
       words_store_be<C::NW>(be, v);
       C::fe_load(x, be);
-      C::curve_rhs(rhs, x);
-      if (C::fe_sqrt(y, rhs)) {
-        C::fe_neg(ny, y);
-        const bool odd = C::fe_is_odd(y);
-        C::fe_select(y, odd == (want_odd != 0), y, ny);
-        found = true;
-      }
+      found = aff::lift_x<C>(y, x, want_odd != 0);
     }
     u32* o = out_xy + i * 2 * C::NW;
     C::fe_store(o, x);

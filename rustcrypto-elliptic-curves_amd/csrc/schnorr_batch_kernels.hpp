@@ -5,7 +5,7 @@
 //   a_i = the first 16 bytes, big-endian, of SHA256(tag || tag || seed32 || be64(i)), tag = SHA256("ecgpu/BIP340/batch-coefficient"),
 //         0 replaced by 1; i is the element's index in the CALLER's batch, so the coefficients do not depend on how a batch is cut.
 //         The state after tag || tag is a constant: one compression per signature.
-//   prep_kernel    one signature per lane: decode as schnorr::verify_prep_kernel, lift r, write terms 2i = (a_i, R_i) and
+//   prep_kernel    one signature per lane: schnorr::decode and lift r (schnorr_kernels.hpp over affine_ops.hpp), write terms 2i = (a_i, R_i) and
 //                  2i + 1 = (a_i e_i mod n, P_i), dec[i], and add t_i = a_i s_i mod n into the lane's wide accumulator.  An element
 //                  that does not decode, or whose r is no x-coordinate, is invalid for the per-signature verifier as well (its R'
 //                  is a curve point with x(R') = r): dec[i] = 0 and it is left out - scalars 0 on the point G, t_i = 0.
@@ -17,6 +17,7 @@
 #pragma once
 #include "h2c_hash.hpp"
 #include "scalar_ops.hpp"
+#include "schnorr_kernels.hpp"
 
 namespace ecgpu {
 namespace schnorr_batch {
@@ -65,35 +66,16 @@ ECGPU_HD void sum_finish(u32* k, const u32* acc) {
   smont::neg<O>(k, r);
 }
 
-// lift_x: y = the even square root of x^3 + 7; returns whether there is one (x is a loaded field element below p)
-ECGPU_HD bool lift_x(FeK256& y, const FeK256& x) {
-  FeK256 rhs, ny;
-  CurveK256::curve_rhs(rhs, x);
-  const bool has = k256::sqrt(y, rhs);
-  k256::neg(ny, y);
-  if (k256::is_odd(y)) y = ny;
-  return has;
-}
-
 // One signature.  px, sig, e: 8 / 16 / 8 words as they lie in memory.  Writes the two scalars (sc: 2 x 8 words) and the two points
 // (pts: 2 x 16 words) of terms 2i and 2i + 1 in the MSM's wire layout and t = a s mod n (limbs; 0 for a left-out element).
 // Returns dec: 1 where r in [1, p) is an x-coordinate, s in [1, n), the key x < p has a square root.
 ECGPU_HD u32 prep_lane(u32* sc, u32* pts, u32* t, const u32* px, const u32* sig, const u32* e, const Seed& seed, u64 index) {
   using O = K256Order;
-  u32 r[8], s[8], x[8], ee[8], ord[8], pm[8];
-  words_load_be<8>(r, sig);
-  words_load_be<8>(s, sig + 8);
-  words_load_be<8>(x, px);
-  words_load_be<8>(ee, e);
-  k256::order(ord);
-  CurveK256::modulus(pm);
-  bool g = !mp_is_zero<8>(r) && !mp_geq<8>(r, pm) && !mp_is_zero<8>(s) && !mp_geq<8>(s, ord) && !mp_geq<8>(x, pm);
+  u32 s[8], ee[8];
   FeK256 fr, yr, fx, yp;
+  bool g = schnorr::decode(s, ee, fx, yp, px, sig, e);
   CurveK256::fe_load(fr, sig);
-  CurveK256::fe_load(fx, px);
-  g = lift_x(yp, fx) && g;
-  g = lift_x(yr, fr) && g;
-  k256::scalar_reduce_once(ee);              // Reduce::reduce_bytes of the challenge hash, once, as the per-signature prep does
+  g = schnorr::lift_even(yr, fr) && g;
   u32 a[8], ae[8];
   coefficient(a, seed, index);
   scops::mul_plain<O>(ae, a, ee);

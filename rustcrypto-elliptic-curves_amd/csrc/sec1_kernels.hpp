@@ -78,29 +78,14 @@ __global__ void __launch_bounds__(256) from_bytes_kernel(const uint8_t* in, u32*
     C::fe_zero(zero);
     x = zero; y = zero;
     if (wide && tag == 4) {
-      u32 lx[NW], ly[NW], p[NW];
-      words_load_be<NW>(lx, raw);
-      words_load_be<NW>(ly, rawy);
-      C::modulus(p);
-      const bool canon = !mp_geq<NW>(lx, p) && !mp_geq<NW>(ly, p);
-      typename C::Fe l, r, d;
       C::fe_load(x, raw);
       C::fe_load(y, rawy);
-      C::fe_sqr(l, y);
-      C::curve_rhs(r, x);
-      C::fe_sub(d, l, r);
-      good = canon && C::fe_is_zero(d);
+      good = aff::coords_canonical<C>(raw, rawy) && aff::on_curve<C>(x, y);
       if (!good) { x = zero; y = zero; }
     } else if (tagged) {
-      u32 lx[NW], p[NW];
-      words_load_be<NW>(lx, raw);
-      C::modulus(p);
-      const bool canon = !mp_geq<NW>(lx, p);
-      typename C::Fe rhs, ny;
+      typename C::Fe ny;
       C::fe_load(x, raw);
-      C::curve_rhs(rhs, x);
-      const bool has = C::fe_sqrt(y, rhs);
-      C::fe_neg(ny, y);
+      const bool has = aff::sqrt_rhs<C>(y, ny, x);
       const bool odd = C::fe_is_odd(y);
       bool keep = (odd == (tag == 3));
       if (tag == 5 && !C::A_IS_ZERO) {
@@ -112,7 +97,7 @@ __global__ void __launch_bounds__(256) from_bytes_kernel(const uint8_t* in, u32*
         keep = mp_geq<NW>(nl, yl);
       }
       C::fe_select(y, keep, y, ny);
-      good = canon && has;
+      good = aff::coords_canonical<C>(raw) && has;
       if (!good) { x = zero; y = zero; }
     } else if (tag == 0 && any == 0 && tail_any == 0) {
       good = true;                                  // the fixed-width identity

@@ -2,6 +2,9 @@
 // of prep_kernel and the wide modular sum, run in the kernel's shape - lanes on a grid stride, 64 lanes to a wave, four waves to a
 // workgroup, one partial per workgroup, then the finish step.  Checked against tests/schnorr_batch_model.py and the oracle by
 // tests/test_hosttwin_schnorr_batch.py; with -DHOSTTWIN_SCHNORR_BATCH_MAIN the file is a program of its own (for a sanitizer build: schnorr_batch_san.mk).
+#ifndef HOSTTWIN_SCHNORR_BATCH_MAIN
+#include "hosttwin_trace.hpp"      // in the library every translation unit builds the shared inline functions with the same hooks
+#endif
 #include <string.h>
 #include <vector>
 #include "schnorr_batch_kernels.hpp"

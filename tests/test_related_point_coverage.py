@@ -6,7 +6,9 @@ change to the vectors, or to a schedule, that silently stops reaching a branch f
 
 Every site in csrc/ has to be reached; there is no exempt list.  (The negated forms of the single-term secp256k1 loop,
 k256::jac_add_mixed_neg, carry no hook: no multi-point schedule calls them, a single term of prime order cannot reach their
-same-point branch, and tests/test_hosttwin_k256_neg_forms.py covers them case by case.)"""
+same-point branch, and tests/test_hosttwin_k256_neg_forms.py covers them case by case.  The sites of csrc/affine_ops.hpp - the sum
+of two affine points after the schedules, and y from x - lie in no schedule: tests/test_hosttwin_sigsum.py enters each of them with
+signatures built for it and pins the counts; here they are only listed, so that a new site still has to be asked for.)"""
 import random
 
 import pytest
@@ -22,6 +24,7 @@ CASES = ("inf", "same", "same:z", "opp", "opp:z")
 FOLD = ["jac.add." + s for s in ("p_inf", "q_inf", "same", "same:z", "opp", "opp:z")]
 FORMULA_ONLY = (["jac.add_affine." + s for s in ("same", "opp")] + ["msm.xyzz_add_mixed." + s for s in CASES]          # no host-walkable schedule calls these
                 + ["msm.xyzz_add." + s for s in ("p_inf", "q_inf", "same", "same:z", "opp", "opp:z")])
+AFFINE_OPS = ["affsum." + s for s in ("both_inf", "one_inf", "same", "opp", "chord")] + ["lift.no_root"]       # csrc/affine_ops.hpp: two affine operands, no schedule; tests/test_hosttwin_sigsum.py enters each on its own rows
 SCHEDULE_SITES = {
     "k256": ["k256.jac_add_mixed." + s for s in CASES] + FOLD,          # straus.hpp and the two-term lane body use the fused secp256k1 form
     "p256": ["jac.add_mixed." + s for s in CASES] + FOLD,
@@ -93,15 +96,15 @@ def test_formulas_reach_every_site_on_family_operands(cn):
             assert g == (M.affine_mul(c, s, fam.base) if s else None), (op, a, b)
     hits = W.exc_counts()
     sites = W.exc_sites_in_source()
-    assert sites == set(SCHEDULE_SITES["k256"]) | set(SCHEDULE_SITES["p256"]) | set(FORMULA_ONLY) and set(hits) <= sites
-    mine = {s for s in sites if not s.startswith("k256.")}               # the fused secp256k1 form has no entry of its own: the schedules above
+    assert sites == set(SCHEDULE_SITES["k256"]) | set(SCHEDULE_SITES["p256"]) | set(FORMULA_ONLY) | set(AFFINE_OPS) and set(hits) <= sites
+    mine = {s for s in sites if not s.startswith("k256.")} - set(AFFINE_OPS)           # the fused secp256k1 form has no entry of its own: the schedules above
     low = {s: hits.get(s, 0) for s in mine if hits.get(s, 0) < MIN_HITS}
     assert not low, (cn, low)
 
 
 def test_every_site_is_asked_for():
     """a new ECGPU_EXC_NOTE site in csrc/ has to be added to a list above"""
-    asked = set(SCHEDULE_SITES["k256"]) | set(SCHEDULE_SITES["p256"]) | set(SCHEDULE_SITES["p384"]) | set(FORMULA_ONLY)
+    asked = set(SCHEDULE_SITES["k256"]) | set(SCHEDULE_SITES["p256"]) | set(SCHEDULE_SITES["p384"]) | set(FORMULA_ONLY) | set(AFFINE_OPS)
     assert W.exc_sites_in_source() == asked
 
 
