@@ -22,7 +22,8 @@
  *  - `mem` says where the caller's buffers live: ECGPU_MEM_HOST (the library stages them
  *    through HBM) or ECGPU_MEM_DEVICE (pointers into this GPU's HBM, 4-byte aligned - ecgpu_msm
  *    additionally wants its AFFINE points 16-byte aligned; the call is asynchronous on the
- *    context's stream).
+ *    context's stream).  The byte-record buffers - `out` of ecgpu_to_bytes_batch / ecgpu_sec1_encode_batch
+ *    and `in` of ecgpu_from_bytes_batch / ecgpu_sec1_decode_batch - may have any alignment.
  *  - Every function returns 0 on success or a negative ecgpu_status; ecgpu_last_error() gives
  *    the text.  Arithmetic on valid inputs cannot fail.  Decoding failures (scalar >= n,
  *    coordinate >= p, point not on the curve) are reported per element by the *_validate
