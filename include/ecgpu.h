@@ -441,13 +441,18 @@ int ecgpu_map_to_curve_batch(ecgpu_ctx* ctx, int curve, const uint8_t* u, int co
  * Err, and so is dst_len > 255 - the RFC's rehash of an oversize DST ("H2C-OVERSIZE-DST-") is not implemented.  It travels to
  * the kernels in their argument block.
  * Constant time in the messages: no branch and no address depends on a message byte; the lengths are public. */
-typedef enum ecgpu_hash { ECGPU_SHA256 = 0, ECGPU_SHA384 = 1 } ecgpu_hash;
+typedef enum ecgpu_hash { ECGPU_SHA256 = 0, ECGPU_SHA384 = 1,
+                          /* the sponge family (csrc/keccak.hpp) starts at 16; ids 2 .. 15 and everything above 18 are refused */
+                          ECGPU_KECCAK256 = 16, ECGPU_SHA3_256 = 17, ECGPU_SHA3_384 = 18 } ecgpu_hash;
+/* digest size of a hash in bytes (32, 48, 32, 32, 48), 0 for an unknown id */
+size_t ecgpu_hash_bytes(int hash);
 enum {
   ECGPU_H2C_RO = 0, /* hash_from_bytes: two maps and their sum */
   ECGPU_H2C_NU = 1  /* encode_from_bytes: one map */
 };
 /* ExpandMsgXmd::expand_message (external elliptic-curve crate, hash2curve/hash2field/expand_msg/xmd.rs; RFC 9380 5.3.1):
- * out[i] = out_bytes uniform bytes of message i, 1 <= out_bytes <= 255 digests (8160 for SHA-256, 12240 for SHA-384). */
+ * out[i] = out_bytes uniform bytes of message i, 1 <= out_bytes <= 255 digests (8160 for SHA-256, 12240 for SHA-384).  XMD is the
+ * Merkle-Damgard expander: the sponge ids are refused (expand_message_xof is out of scope). */
 int ecgpu_expand_message_xmd_batch(ecgpu_ctx* ctx, int hash, const uint8_t* msgs, size_t msg_stride, const uint32_t* msg_len,
                                    const uint8_t* dst, size_t dst_len, uint8_t* out, size_t out_bytes, size_t n, int mem);
 /* FromOkm for FieldElement (k256|p256|p384/src/arithmetic/hash2curve.rs: from_okm): okm = n big-endian records of L bytes
@@ -466,17 +471,21 @@ int ecgpu_hash_to_scalar_batch(ecgpu_ctx* ctx, int curve, const uint8_t* msgs, s
                                const uint8_t* dst, size_t dst_len, uint8_t* out, size_t n, int mem);
 
 /* ---- from message bytes: digests, ECDSA and BIP340 ------------------------------------------------------------------
- * Digest::digest for a batch: out[i] = SHA-256 (32 bytes) or SHA-384 (48 bytes) of message i, one message per lane.  The message
+ * Digest::digest for a batch: out[i] = the digest of message i, one message per lane: SHA-256 (32 bytes), SHA-384 (48), Keccak-256
+ * (32), SHA3-256 (32) or SHA3-384 (48).  ECGPU_KECCAK256 is Keccak with its original padding - the `sha3` crate's Keccak256,
+ * Ethereum's hash - and NOT FIPS 202 SHA3-256: the two differ in one padding byte.  The message
  * arguments follow the rules above (ragged batches, msg_stride = 0, the refusal of a host-side msg_len[i] > msg_stride, a stride
  * below 2^32).  A record that is 4-byte aligned has its whole blocks read by 32-bit words, any other one byte by byte
- * (csrc/sha2.hpp, update_aligned): pad the stride to a multiple of 4 (host batches are staged from an aligned base) where the
- * messages are long.  `out` is 4-byte aligned in device memory (a prehash call reads its rows as words); refused otherwise. */
+ * (csrc/sha2.hpp and csrc/keccak.hpp, update_aligned; a block is 64, 128, 136, 136, 104 bytes): pad the stride to a multiple of 4
+ * (host batches are staged from an aligned base) where the messages are long.  `out` is 4-byte aligned in device memory (a prehash
+ * call reads its rows as words); refused otherwise. */
 int ecgpu_digest_batch(ecgpu_ctx* ctx, int hash, const uint8_t* msgs, size_t msg_stride, const uint32_t* msg_len,
                        uint8_t* out, size_t n, int mem);
 /* The message-level trait items of the reference: the digest kernel writes the curve's own digest (SHA-256 for secp256k1 and
  * P-256, SHA-384 for P-384: DigestPrimitive::Digest, k256 | p256 | p384 src/ecdsa.rs) into the context's hash workspace, then
  * the prehash call's pipeline runs on it, with that call's flags, outputs and chunking.  The digest is field-sized, so bits2field
- * is the identity.  Any other digest stays with the prehash calls.  Messages and digests are public: nothing of them is cleared.
+ * is the identity.  Another digest of the same size goes through the ecgpu_ecdsa_*_digest_batch calls below, every other one stays
+ * with the prehash calls.  Messages and digests are public: nothing of them is cleared.
  *
  * Signer::sign (extra == NULL) / RandomizedSigner::sign_with_rng (extra given) of ecdsa::SigningKey (external ecdsa crate,
  * src/signing.rs: try_sign hashes with C::Digest and enters sign_prehash): everything else as ecgpu_ecdsa_sign_prehash_batch -
@@ -494,6 +503,23 @@ int ecgpu_ecdsa_verify_msg_batch(ecgpu_ctx* ctx, int curve, const uint8_t* msgs,
 int ecgpu_ecdsa_recover_msg_batch(ecgpu_ctx* ctx, int curve, const uint8_t* msgs, size_t msg_stride, const uint32_t* msg_len,
                                   const uint8_t* sig_rs, const uint8_t* recovery_id, uint8_t* pubkeys_xy, uint8_t* ok,
                                   size_t n, int mem, unsigned flags);
+/* The same three calls on a chosen digest: DigestSigner::sign_digest, sign_digest_recoverable and RandomizedDigestSigner (extra
+ * given), DigestVerifier::verify_digest and VerifyingKey::recover_from_digest of the external ecdsa crate, as the reference's
+ * Ethereum example uses them with Keccak256::new_with_prefix(msg) (k256/src/ecdsa.rs:84-143, 312-342).  `hash` must have a digest
+ * of exactly ecgpu_field_bytes(curve) bytes - the reference's bound D: Digest<OutputSize = FieldBytesSize<C>> - so secp256k1 and
+ * P-256 take ECGPU_SHA256, ECGPU_KECCAK256 and ECGPU_SHA3_256, P-384 takes ECGPU_SHA384 and ECGPU_SHA3_384; any other pairing and
+ * any unknown id is ECGPU_ERR_ARG.  The RFC 6979 nonce keeps the curve's own HMAC-DRBG hash (HMAC-SHA-256 on secp256k1 and P-256,
+ * HMAC-SHA-384 on P-384) whatever `hash` is, as in the reference.  Everything behind the digest is the *_msg_batch call; with
+ * hash = the curve's own digest the results are those of the *_msg_batch call, byte for byte. */
+int ecgpu_ecdsa_sign_digest_batch(ecgpu_ctx* ctx, int curve, int hash, const uint8_t* secret_d, const uint8_t* msgs,
+                                  size_t msg_stride, const uint32_t* msg_len, const uint8_t* extra, uint8_t* sig_rs,
+                                  uint8_t* recovery_id, uint8_t* ok, size_t n, int mem, unsigned flags);
+int ecgpu_ecdsa_verify_digest_batch(ecgpu_ctx* ctx, int curve, int hash, const uint8_t* msgs, size_t msg_stride,
+                                    const uint32_t* msg_len, const uint8_t* sig_rs, const uint8_t* pubkeys_xy, uint8_t* ok,
+                                    size_t n, int mem, unsigned flags);
+int ecgpu_ecdsa_recover_digest_batch(ecgpu_ctx* ctx, int curve, int hash, const uint8_t* msgs, size_t msg_stride,
+                                     const uint32_t* msg_len, const uint8_t* sig_rs, const uint8_t* recovery_id,
+                                     uint8_t* pubkeys_xy, uint8_t* ok, size_t n, int mem, unsigned flags);
 /* Signer::try_sign (aux_rand == NULL: the reference passes Default::default(), 32 zero bytes) / RandomizedSigner::try_sign_with_rng
  * (aux_rand given) of k256's schnorr::SigningKey (k256/src/schnorr/signing.rs:214-218): sign_prehash_with_aux_rand over
  * Sha256::new_with_prefix(msg), i.e. ecgpu_schnorr_sign_prehash_batch on SHA256(msg).  This is the reference's behaviour - BIP340

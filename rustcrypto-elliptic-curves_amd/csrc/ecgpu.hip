@@ -176,13 +176,20 @@ static const ecgpu_curve_ops* ops_for(int curve) {
 
 extern "C" {
 
-const char* ecgpu_version(void) { return "ecgpu 0.9 (gfx950)"; }
+const char* ecgpu_version(void) { return "ecgpu 0.10 (gfx950)"; }
 
 size_t ecgpu_field_bytes(int curve) {
   switch (curve) {
     case ECGPU_K256: return 32;
     case ECGPU_P256: return 32;
     case ECGPU_P384: return 48;
+    default: return 0;
+  }
+}
+size_t ecgpu_hash_bytes(int hash) {
+  switch (hash) {
+    case ECGPU_SHA256: case ECGPU_KECCAK256: case ECGPU_SHA3_256: return 32;
+    case ECGPU_SHA384: case ECGPU_SHA3_384: return 48;
     default: return 0;
   }
 }
@@ -854,40 +861,62 @@ int ecgpu_schnorr_verify_prehash_batch(ecgpu_ctx* c, int curve, const uint8_t* p
 }
 
 // ---------------------------------------------------------------------------------------------
-// message level (include/ecgpu.h, "from message bytes"): the digest kernel writes the curve's own digest of every message into the
-// hash workspace, then the prehash form's launcher runs on it.  Messages and digests are public: nothing of them is wiped.
+// message level (include/ecgpu.h, "from message bytes"): the digest kernel writes the digest of every message - the curve's own, or
+// for the *_digest_batch calls a chosen one of the same size - into the hash workspace, then the prehash form's launcher runs on it.
+// Messages and digests are public: nothing of them is wiped.
 // ---------------------------------------------------------------------------------------------
 int ecgpu_digest_batch(ecgpu_ctx* c, int hash, const uint8_t* msgs, size_t msg_stride, const uint32_t* msg_len, uint8_t* out, size_t n, int mem) {
   if (!c || !out) return ecgpu_set_err(c, ECGPU_ERR_ARG, "null argument");
-  if (hash != ECGPU_SHA256 && hash != ECGPU_SHA384) return ecgpu_set_err(c, ECGPU_ERR_ARG, "unknown hash %d", hash);
+  if (!ecgpu_hash_bytes(hash)) return ecgpu_set_err(c, ECGPU_ERR_ARG, "unknown hash %d", hash);
   if (mem == ECGPU_MEM_DEVICE && ((uintptr_t)out & 3u)) return ecgpu_set_err(c, ECGPU_ERR_ARG, "ecgpu_digest_batch: device-resident digests are 4-byte aligned");
   int rc = msgs_enter(c, msgs, msg_stride, msg_len, n, mem);
   if (rc) return rc;
   if (n == 0) return ECGPU_OK;
   std::lock_guard<std::mutex> lk(c->mu);
   HIPCHK(c, hipSetDevice(c->device));
-  const CallArg args[] = {arg_in(msg_stride ? msgs : nullptr, msg_stride, ARG_OPTIONAL), arg_in(msg_len, 4, ARG_OPTIONAL), arg_out(out, hash == ECGPU_SHA384 ? 48 : 32)};
+  const CallArg args[] = {arg_in(msg_stride ? msgs : nullptr, msg_stride, ARG_OPTIONAL), arg_in(msg_len, 4, ARG_OPTIONAL), arg_out(out, ecgpu_hash_bytes(hash))};
   return run_batch(c, mem, n, args, (size_t)1 << 22, [&](void** d, size_t cnt) {
     return ecgpuint_digest(c, hash, (const uint8_t*)d[0], msg_stride, (const uint32_t*)d[1], (uint32_t*)d[2], cnt);
   });
 }
-// z = cnt digests of the curve's own hash in the hash workspace (the prehash launchers carve ecdsa_ws, never hash_ws)
-static int digest_to_ws(ecgpu_ctx* c, int curve, const void* msgs, size_t msg_stride, const void* msg_len, size_t cnt, uint32_t** z, uint32_t** more = nullptr) {
+// z = cnt digests of `hash` in the hash workspace (the prehash launchers carve ecdsa_ws, never hash_ws); the rows are field-sized
+static int digest_to_ws(ecgpu_ctx* c, int curve, int hash, const void* msgs, size_t msg_stride, const void* msg_len, size_t cnt, uint32_t** z, uint32_t** more = nullptr) {
   const size_t nb = ecgpu_field_bytes(curve);
   int rc = ecgpu_carve(c, c->hash_ws, [&](WsCarver& ws) {
     *z = ws.take<uint32_t>(cnt * nb);
     if (more) *more = ws.take<uint32_t>(cnt * nb);
   });
   if (rc) return rc;
-  return ecgpuint_digest(c, curve_hash(curve), (const uint8_t*)msgs, msg_stride, (const uint32_t*)msg_len, *z, cnt);
+  return ecgpuint_digest(c, hash, (const uint8_t*)msgs, msg_stride, (const uint32_t*)msg_len, *z, cnt);
 }
-int ecgpu_ecdsa_sign_msg_batch(ecgpu_ctx* c, int curve, const uint8_t* secret_d, const uint8_t* msgs, size_t msg_stride, const uint32_t* msg_len,
-                               const uint8_t* extra, uint8_t* sig_rs, uint8_t* recovery_id, uint8_t* ok, size_t n, int mem, unsigned flags) {
+static const char* hash_name(int hash) {
+  switch (hash) {
+    case ECGPU_SHA256: return "SHA-256";
+    case ECGPU_SHA384: return "SHA-384";
+    case ECGPU_KECCAK256: return "Keccak-256";
+    case ECGPU_SHA3_256: return "SHA3-256";
+    case ECGPU_SHA3_384: return "SHA3-384";
+    default: return "unknown";
+  }
+}
+static const char* curve_name(int curve) { return curve == ECGPU_K256 ? "secp256k1" : curve == ECGPU_P256 ? "P-256" : curve == ECGPU_P384 ? "P-384" : "unknown"; }
+// the reference's bound D: Digest<OutputSize = FieldBytesSize<C>>: the digest fills the field (an unknown curve is ENTER's to refuse)
+static int hash_fits(ecgpu_ctx* c, const char* what, int curve, int hash) {
+  const size_t hb = ecgpu_hash_bytes(hash), nb = ecgpu_field_bytes(curve);
+  if (!hb) return ecgpu_set_err(c, ECGPU_ERR_ARG, "%s: unknown hash %d", what, hash);
+  if (nb && hb != nb)
+    return ecgpu_set_err(c, ECGPU_ERR_ARG, "%s: %s gives %zu bytes, %s takes a digest of %zu (hash %d, curve %d)", what, hash_name(hash), hb, curve_name(curve), nb, hash, curve);
+  return 0;
+}
+// sign / verify / recover from message bytes on `hash`: the *_msg_batch calls are the case hash = curve_hash(curve)
+static int sign_from_msgs(ecgpu_ctx* c, const char* what, int curve, int hash, const uint8_t* secret_d, const uint8_t* msgs, size_t msg_stride, const uint32_t* msg_len,
+                          const uint8_t* extra, uint8_t* sig_rs, uint8_t* recovery_id, uint8_t* ok, size_t n, int mem, unsigned flags) {
   if (!c || !secret_d || !sig_rs || !ok) return ecgpu_set_err(c, ECGPU_ERR_ARG, "null argument");
-  if (flags & ECGPU_PUBLIC_SCALARS)
-    return ecgpu_set_err(c, ECGPU_ERR_ARG, "ecgpu_ecdsa_sign_msg_batch: ECGPU_PUBLIC_SCALARS is refused (a nonce derived from the key is never public)");
-  int rc = msgs_enter(c, msgs, msg_stride, msg_len, n, mem);
+  int rc = hash_fits(c, what, curve, hash);
   if (rc) return rc;
+  if (flags & ECGPU_PUBLIC_SCALARS)
+    return ecgpu_set_err(c, ECGPU_ERR_ARG, "%s: ECGPU_PUBLIC_SCALARS is refused (a nonce derived from the key is never public)", what);
+  if ((rc = msgs_enter(c, msgs, msg_stride, msg_len, n, mem))) return rc;
   if (n == 0) return ECGPU_OK;
   ENTER(c, curve);
   const CallArg args[] = {arg_in(secret_d, nb, ARG_SECRET), arg_in(msg_stride ? msgs : nullptr, msg_stride, ARG_OPTIONAL), arg_in(msg_len, 4, ARG_OPTIONAL),
@@ -895,42 +924,69 @@ int ecgpu_ecdsa_sign_msg_batch(ecgpu_ctx* c, int curve, const uint8_t* secret_d,
   const unsigned fb_flags = (flags & ECGPU_EXACT_REFERENCE) ? (unsigned)ECGPU_EXACT_REFERENCE : (unsigned)ECGPU_SECRET_SCALARS;
   return run_batch(c, mem, n, args, ops->pass_units(c, 0, 1, fb_flags), [&](void** d, size_t cnt) {
     uint32_t* z;
-    int r = digest_to_ws(c, curve, d[1], msg_stride, d[2], cnt, &z);
+    int r = digest_to_ws(c, curve, hash, d[1], msg_stride, d[2], cnt, &z);
     if (r) return r;
     return ops->ecdsa_sign_prehash(c, (const uint32_t*)d[0], z, (const uint32_t*)d[3], (uint32_t*)d[4], (uint8_t*)d[5], (uint8_t*)d[6], cnt, flags);
   });
 }
-int ecgpu_ecdsa_verify_msg_batch(ecgpu_ctx* c, int curve, const uint8_t* msgs, size_t msg_stride, const uint32_t* msg_len, const uint8_t* sig_rs,
-                                 const uint8_t* pubkeys_xy, uint8_t* ok, size_t n, int mem, unsigned flags) {
+static int verify_from_msgs(ecgpu_ctx* c, const char* what, int curve, int hash, const uint8_t* msgs, size_t msg_stride, const uint32_t* msg_len, const uint8_t* sig_rs,
+                            const uint8_t* pubkeys_xy, uint8_t* ok, size_t n, int mem, unsigned flags) {
   if (!c || !sig_rs || !pubkeys_xy || !ok) return ecgpu_set_err(c, ECGPU_ERR_ARG, "null argument");
-  int rc = msgs_enter(c, msgs, msg_stride, msg_len, n, mem);
+  int rc = hash_fits(c, what, curve, hash);
   if (rc) return rc;
+  if ((rc = msgs_enter(c, msgs, msg_stride, msg_len, n, mem))) return rc;
   if (n == 0) return ECGPU_OK;
   ENTER(c, curve);
   const CallArg args[] = {arg_in(msg_stride ? msgs : nullptr, msg_stride, ARG_OPTIONAL), arg_in(msg_len, 4, ARG_OPTIONAL), arg_in(sig_rs, 2 * nb),
                           arg_in(pubkeys_xy, 2 * nb), arg_out(ok, 1)};
   return run_batch(c, mem, n, args, ops->pass_units(c, 1, 1, 0), [&](void** d, size_t cnt) {
     uint32_t* z;
-    int r = digest_to_ws(c, curve, d[0], msg_stride, d[1], cnt, &z);
+    int r = digest_to_ws(c, curve, hash, d[0], msg_stride, d[1], cnt, &z);
     if (r) return r;
     return ops->ecdsa_verify(c, z, (const uint32_t*)d[2], (const uint32_t*)d[3], (uint8_t*)d[4], cnt, flags);
   });
 }
-int ecgpu_ecdsa_recover_msg_batch(ecgpu_ctx* c, int curve, const uint8_t* msgs, size_t msg_stride, const uint32_t* msg_len, const uint8_t* sig_rs,
-                                  const uint8_t* recovery_id, uint8_t* pubkeys_xy, uint8_t* ok, size_t n, int mem, unsigned flags) {
+static int recover_from_msgs(ecgpu_ctx* c, const char* what, int curve, int hash, const uint8_t* msgs, size_t msg_stride, const uint32_t* msg_len, const uint8_t* sig_rs,
+                             const uint8_t* recovery_id, uint8_t* pubkeys_xy, uint8_t* ok, size_t n, int mem, unsigned flags) {
   if (!c || !sig_rs || !recovery_id || !pubkeys_xy || !ok) return ecgpu_set_err(c, ECGPU_ERR_ARG, "null argument");
-  int rc = msgs_enter(c, msgs, msg_stride, msg_len, n, mem);
+  int rc = hash_fits(c, what, curve, hash);
   if (rc) return rc;
+  if ((rc = msgs_enter(c, msgs, msg_stride, msg_len, n, mem))) return rc;
   if (n == 0) return ECGPU_OK;
   ENTER(c, curve);
   const CallArg args[] = {arg_in(msg_stride ? msgs : nullptr, msg_stride, ARG_OPTIONAL), arg_in(msg_len, 4, ARG_OPTIONAL), arg_in(sig_rs, 2 * nb),
                           arg_in(recovery_id, 1), arg_out(pubkeys_xy, 2 * nb), arg_out(ok, 1)};
   return run_batch(c, mem, n, args, ops->pass_units(c, 1, 1, 0), [&](void** d, size_t cnt) {
     uint32_t* z;
-    int r = digest_to_ws(c, curve, d[0], msg_stride, d[1], cnt, &z);
+    int r = digest_to_ws(c, curve, hash, d[0], msg_stride, d[1], cnt, &z);
     if (r) return r;
     return ops->ecdsa_recover(c, z, (const uint32_t*)d[2], (const uint8_t*)d[3], (uint32_t*)d[4], (uint8_t*)d[5], cnt, flags);
   });
+}
+int ecgpu_ecdsa_sign_msg_batch(ecgpu_ctx* c, int curve, const uint8_t* secret_d, const uint8_t* msgs, size_t msg_stride, const uint32_t* msg_len,
+                               const uint8_t* extra, uint8_t* sig_rs, uint8_t* recovery_id, uint8_t* ok, size_t n, int mem, unsigned flags) {
+  return sign_from_msgs(c, "ecgpu_ecdsa_sign_msg_batch", curve, curve_hash(curve), secret_d, msgs, msg_stride, msg_len, extra, sig_rs, recovery_id, ok, n, mem, flags);
+}
+int ecgpu_ecdsa_verify_msg_batch(ecgpu_ctx* c, int curve, const uint8_t* msgs, size_t msg_stride, const uint32_t* msg_len, const uint8_t* sig_rs,
+                                 const uint8_t* pubkeys_xy, uint8_t* ok, size_t n, int mem, unsigned flags) {
+  return verify_from_msgs(c, "ecgpu_ecdsa_verify_msg_batch", curve, curve_hash(curve), msgs, msg_stride, msg_len, sig_rs, pubkeys_xy, ok, n, mem, flags);
+}
+int ecgpu_ecdsa_recover_msg_batch(ecgpu_ctx* c, int curve, const uint8_t* msgs, size_t msg_stride, const uint32_t* msg_len, const uint8_t* sig_rs,
+                                  const uint8_t* recovery_id, uint8_t* pubkeys_xy, uint8_t* ok, size_t n, int mem, unsigned flags) {
+  return recover_from_msgs(c, "ecgpu_ecdsa_recover_msg_batch", curve, curve_hash(curve), msgs, msg_stride, msg_len, sig_rs, recovery_id, pubkeys_xy, ok, n, mem, flags);
+}
+// DigestSigner / RandomizedDigestSigner, DigestVerifier and recover_from_digest on a digest of the field's size (include/ecgpu.h)
+int ecgpu_ecdsa_sign_digest_batch(ecgpu_ctx* c, int curve, int hash, const uint8_t* secret_d, const uint8_t* msgs, size_t msg_stride, const uint32_t* msg_len,
+                                  const uint8_t* extra, uint8_t* sig_rs, uint8_t* recovery_id, uint8_t* ok, size_t n, int mem, unsigned flags) {
+  return sign_from_msgs(c, "ecgpu_ecdsa_sign_digest_batch", curve, hash, secret_d, msgs, msg_stride, msg_len, extra, sig_rs, recovery_id, ok, n, mem, flags);
+}
+int ecgpu_ecdsa_verify_digest_batch(ecgpu_ctx* c, int curve, int hash, const uint8_t* msgs, size_t msg_stride, const uint32_t* msg_len, const uint8_t* sig_rs,
+                                    const uint8_t* pubkeys_xy, uint8_t* ok, size_t n, int mem, unsigned flags) {
+  return verify_from_msgs(c, "ecgpu_ecdsa_verify_digest_batch", curve, hash, msgs, msg_stride, msg_len, sig_rs, pubkeys_xy, ok, n, mem, flags);
+}
+int ecgpu_ecdsa_recover_digest_batch(ecgpu_ctx* c, int curve, int hash, const uint8_t* msgs, size_t msg_stride, const uint32_t* msg_len, const uint8_t* sig_rs,
+                                     const uint8_t* recovery_id, uint8_t* pubkeys_xy, uint8_t* ok, size_t n, int mem, unsigned flags) {
+  return recover_from_msgs(c, "ecgpu_ecdsa_recover_digest_batch", curve, hash, msgs, msg_stride, msg_len, sig_rs, recovery_id, pubkeys_xy, ok, n, mem, flags);
 }
 // aux_rand == NULL is the reference's Default::default(), 32 zero bytes per key: the hash workspace holds them behind the digests
 int ecgpu_schnorr_sign_msg_batch(ecgpu_ctx* c, int curve, const uint8_t* secret_keys, const uint8_t* msgs, size_t msg_stride, const uint32_t* msg_len,
@@ -946,7 +1002,7 @@ int ecgpu_schnorr_sign_msg_batch(ecgpu_ctx* c, int curve, const uint8_t* secret_
                           arg_in(aux_rand, 32, ARG_SECRET | ARG_OPTIONAL), arg_out(sig_rs, 2 * nb), arg_out(pubkeys_x, nb, ARG_OPTIONAL), arg_out(ok, 1)};
   return run_batch(c, mem, n, args, ops->pass_units(c, 0, 1, ECGPU_SECRET_SCALARS), [&](void** d, size_t cnt) {
     uint32_t *m, *zero_aux = nullptr;
-    int r = digest_to_ws(c, curve, d[1], msg_stride, d[2], cnt, &m, d[3] ? nullptr : &zero_aux);
+    int r = digest_to_ws(c, curve, ECGPU_SHA256, d[1], msg_stride, d[2], cnt, &m, d[3] ? nullptr : &zero_aux);
     if (r) return r;
     if (zero_aux) HIPCHK(c, hipMemsetAsync(zero_aux, 0, cnt * 32, c->stream));
     return ops->schnorr_sign_prehash(c, (const uint32_t*)d[0], m, d[3] ? (const uint32_t*)d[3] : zero_aux, (uint32_t*)d[4], (uint32_t*)d[5], (uint8_t*)d[6], cnt);
@@ -966,7 +1022,7 @@ int ecgpu_schnorr_verify_msg_batch(ecgpu_ctx* c, int curve, const uint8_t* pubke
   return run_batch(c, mem, n, args, ops->pass_units(c, 1, 1, 0), [&](void** d, size_t cnt) {
     // the digests and the challenges live through schnorr_verify, which carves ecdsa_ws: both come from ONE carve of hash_ws
     uint32_t *m, *e;
-    int r = digest_to_ws(c, curve, d[1], msg_stride, d[2], cnt, &m, &e);
+    int r = digest_to_ws(c, curve, ECGPU_SHA256, d[1], msg_stride, d[2], cnt, &m, &e);
     if (r) return r;
     if ((r = ops->schnorr_challenge(c, (const uint32_t*)d[0], (const uint32_t*)d[3], m, e, cnt))) return r;
     return ops->schnorr_verify(c, (const uint32_t*)d[0], (const uint32_t*)d[3], e, (uint8_t*)d[4], cnt);
@@ -1083,7 +1139,7 @@ int ecgpu_schnorr_batch_verify_msg(ecgpu_ctx* c, int curve, const uint8_t* pubke
                           arg_in(sig_rs, 2 * nb), arg_out(ok, 1, ARG_OPTIONAL)};
   rc = run_batch(c, mem, n, args, SCHNORR_BATCH_PASS, [&](void** d, size_t cnt) {
     uint32_t *m, *e;
-    int r = digest_to_ws(c, curve, d[1], msg_stride, d[2], cnt, &m, &e);
+    int r = digest_to_ws(c, curve, ECGPU_SHA256, d[1], msg_stride, d[2], cnt, &m, &e);
     if (r) return r;
     if ((r = ops->schnorr_challenge(c, (const uint32_t*)d[0], (const uint32_t*)d[3], m, e, cnt))) return r;
     return b.chunk(d[0], d[3], e, d[4], cnt);

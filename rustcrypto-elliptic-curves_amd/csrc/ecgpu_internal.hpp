@@ -223,6 +223,8 @@ constexpr size_t ECGPU_SCHNORR_BATCH_MIN = (size_t)1 << 18;
 int ecgpuint_xmd(ecgpu_ctx* c, int hash, const uint8_t* msgs, size_t msg_stride, const uint32_t* msg_len, const ecgpu::h2c::XmdTail& tail, uint8_t* out, size_t n);
 // plain digests on `hash` (h2c_hash.hip): out = n rows of 32 / 48 bytes, 4-byte aligned
 int ecgpuint_digest(ecgpu_ctx* c, int hash, const uint8_t* msgs, size_t msg_stride, const uint32_t* msg_len, uint32_t* out, size_t n);
+// the sponge ids of ecgpuint_digest (keccak.hip): Keccak-256, SHA3-256, SHA3-384; any other id is refused
+int ecgpuint_keccak_digest(ecgpu_ctx* c, int hash, const uint8_t* msgs, size_t msg_stride, const uint32_t* msg_len, uint32_t* out, size_t n);
 // Pippenger MSM, one translation unit per curve (msm_*.hip); `mul` is the curve's batch scalar multiplication (affine in / out
 // on device memory), used for small sums
 typedef int (*ecgpu_msm_mul_fn)(ecgpu_ctx* c, const uint32_t* scalars, const uint32_t* points, int pt_fmt, uint32_t* out_xy, size_t n);

@@ -20,7 +20,7 @@ int ecgpuint_digest(ecgpu_ctx* c, int hash, const uint8_t* msgs, size_t msg_stri
   switch (hash) {
     case ECGPU_SHA256: hipLaunchKernelGGL((h2c::digest_kernel<sha2::Sha256>), dim3(g), dim3(256), 0, c->stream, msgs, msg_stride, msg_len, out, n); break;
     case ECGPU_SHA384: hipLaunchKernelGGL((h2c::digest_kernel<sha2::Sha384>), dim3(g), dim3(256), 0, c->stream, msgs, msg_stride, msg_len, out, n); break;
-    default: return ecgpu_set_err(c, ECGPU_ERR_ARG, "unknown hash %d", hash);
+    default: return ecgpuint_keccak_digest(c, hash, msgs, msg_stride, msg_len, out, n);                    // the sponge family, or "unknown hash"
   }
   HIPCHK(c, hipGetLastError());
   return 0;

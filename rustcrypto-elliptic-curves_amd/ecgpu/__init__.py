@@ -38,10 +38,11 @@ SC_MUL, SC_SQR, SC_ADD, SC_SUB, SC_NEG, SC_INV, SC_SQRT = range(7)      # ecgpu_
 SC_BINARY = (SC_MUL, SC_ADD, SC_SUB)
 REDUCE_NONZERO = 1
 SHA256, SHA384 = 0, 1                                                  # ecgpu_hash
+KECCAK256, SHA3_256, SHA3_384 = 16, 17, 18                             # the sponge family (csrc/keccak.hpp); Keccak-256 is Ethereum's hash, not SHA3-256
 H2C_RO, H2C_NU = 0, 1                                                  # hash_from_bytes / encode_from_bytes
 CURVE_HASH = {K256: SHA256, P256: SHA256, P384: SHA384}                # the hash of the curve's RFC 9380 suite
 OKM_BYTES = {K256: 48, P256: 48, P384: 72}                             # FromOkm::Length
-DIGEST_BYTES = {SHA256: 32, SHA384: 48}
+DIGEST_BYTES = {SHA256: 32, SHA384: 48, KECCAK256: 32, SHA3_256: 32, SHA3_384: 48}
 # ecgpu_option (per-context tuning / test knobs, include/ecgpu.h)
 OPT_FB_WINDOW, OPT_FB_MAX_WINDOW, OPT_MSM_WINDOW_BITS, OPT_MSM_SLAB_TERMS, OPT_MSM_SMALL_PATH, OPT_MSM_ROUNDS, OPT_K256_WAVES, OPT_FB_MEMORY_BUDGET, OPT_LINCOMB_TERM_BY_TERM = range(9)
 
@@ -103,6 +104,8 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
     lib.ecgpu_version.restype = ctypes.c_char_p
     lib.ecgpu_field_bytes.argtypes = [i]
     lib.ecgpu_field_bytes.restype = sz
+    lib.ecgpu_hash_bytes.argtypes = [i]
+    lib.ecgpu_hash_bytes.restype = sz
     lib.ecgpu_host_alloc.argtypes = [vp, sz, ctypes.POINTER(vp)]
     lib.ecgpu_host_free.argtypes = [vp, vp]
     lib.ecgpu_debug_workspace.argtypes = [vp, i, vp, sz, ctypes.POINTER(sz)]
@@ -162,6 +165,9 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
     lib.ecgpu_ecdsa_sign_msg_batch.argtypes = [vp, i, u8p, u8p, sz, u8p, u8p, u8p, u8p, u8p, sz, i, ctypes.c_uint]
     lib.ecgpu_ecdsa_verify_msg_batch.argtypes = [vp, i, u8p, sz, u8p, u8p, u8p, u8p, sz, i, ctypes.c_uint]
     lib.ecgpu_ecdsa_recover_msg_batch.argtypes = [vp, i, u8p, sz, u8p, u8p, u8p, u8p, u8p, sz, i, ctypes.c_uint]
+    lib.ecgpu_ecdsa_sign_digest_batch.argtypes = [vp, i, i, u8p, u8p, sz, u8p, u8p, u8p, u8p, u8p, sz, i, ctypes.c_uint]
+    lib.ecgpu_ecdsa_verify_digest_batch.argtypes = [vp, i, i, u8p, sz, u8p, u8p, u8p, u8p, sz, i, ctypes.c_uint]
+    lib.ecgpu_ecdsa_recover_digest_batch.argtypes = [vp, i, i, u8p, sz, u8p, u8p, u8p, u8p, u8p, sz, i, ctypes.c_uint]
     lib.ecgpu_schnorr_sign_msg_batch.argtypes = [vp, i, u8p, u8p, sz, u8p, u8p, u8p, u8p, u8p, sz, i]
     lib.ecgpu_schnorr_verify_msg_batch.argtypes = [vp, i, u8p, u8p, sz, u8p, u8p, u8p, sz, i]
     lib.ecgpu_schnorr_batch_verify.argtypes = [vp, i, u8p, u8p, u8p, u8p, u8p, ctypes.POINTER(i), sz, i, ctypes.c_uint]
@@ -184,7 +190,8 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
                  "ecgpu_field_from_okm_batch", "ecgpu_hash_to_curve_batch", "ecgpu_hash_to_scalar_batch", "ecgpu_rfc6979_nonce_batch",
                  "ecgpu_ecdsa_sign_prehash_batch", "ecgpu_schnorr_sign_prehash_batch", "ecgpu_digest_batch", "ecgpu_ecdsa_sign_msg_batch",
                  "ecgpu_ecdsa_verify_msg_batch", "ecgpu_ecdsa_recover_msg_batch", "ecgpu_schnorr_sign_msg_batch", "ecgpu_schnorr_verify_msg_batch",
-                 "ecgpu_schnorr_batch_verify", "ecgpu_schnorr_batch_verify_prehash", "ecgpu_schnorr_batch_verify_msg"):
+                 "ecgpu_schnorr_batch_verify", "ecgpu_schnorr_batch_verify_prehash", "ecgpu_schnorr_batch_verify_msg",
+                 "ecgpu_ecdsa_sign_digest_batch", "ecgpu_ecdsa_verify_digest_batch", "ecgpu_ecdsa_recover_digest_batch"):
         getattr(lib, name).restype = ctypes.c_int
     if path is None:
         _lib = lib
@@ -209,6 +216,7 @@ EXPORTED_SYMBOLS = (
     "ecgpu_digest_batch", "ecgpu_ecdsa_sign_msg_batch", "ecgpu_ecdsa_verify_msg_batch", "ecgpu_ecdsa_recover_msg_batch",
     "ecgpu_schnorr_sign_msg_batch", "ecgpu_schnorr_verify_msg_batch",
     "ecgpu_schnorr_batch_verify", "ecgpu_schnorr_batch_verify_prehash", "ecgpu_schnorr_batch_verify_msg",
+    "ecgpu_hash_bytes", "ecgpu_ecdsa_sign_digest_batch", "ecgpu_ecdsa_verify_digest_batch", "ecgpu_ecdsa_recover_digest_batch",
 )
 
 
@@ -359,11 +367,8 @@ def pack_messages_aligned(msgs: Sequence[bytes]):
     return pack_messages(msgs, (longest + 15) // 16 * 16)
 
 
-DIGEST_BYTES = {0: 32, 1: 48}       # by ecgpu_hash
-
-
 def digest(ctx: "Context", hash_id: int, msgs: Sequence[bytes]) -> np.ndarray:
-    """SHA-256 / SHA-384 of every message on the device -> (n, 32 | 48) digests (ecgpu_digest_batch)"""
+    """SHA-256 / SHA-384 / Keccak-256 / SHA3-256 / SHA3-384 of every message on the device -> (n, 32 | 48) digests (ecgpu_digest_batch)"""
     rec, lens, stride = pack_messages_aligned(msgs)
     out = _host_out(len(msgs), DIGEST_BYTES.get(hash_id, 48))
     ctx.check(ctx.lib.ecgpu_digest_batch(ctx.handle, hash_id, _ptr(rec)[0] if stride else None, stride, _ptr(lens)[0], _ptr(out)[0], len(msgs), HOST))
@@ -707,6 +712,11 @@ class Curve:
                                                               len(z), HOST, fl))
         return out, ok
 
+    def ecdsa_recover_device(self, d_prehash, d_sig_rs, d_recid, d_pubkeys_xy, d_ok, n: int, flags: Optional[int] = None):
+        fl = self.default_ecdsa_flags() if flags is None else flags
+        self.ctx.check(self.ctx.lib.ecgpu_ecdsa_recover_batch(self.ctx.handle, self.id, _ptr(d_prehash)[0], _ptr(d_sig_rs)[0], _ptr(d_recid)[0],
+                                                              _ptr(d_pubkeys_xy)[0], _ptr(d_ok)[0], n, DEVICE, fl))
+
     def schnorr_verify(self, pubkeys_x, sig_rs, challenges) -> np.ndarray:
         """EC part of BIP340 verification; challenges = tagged challenge hashes (ecgpu.schnorr computes them)."""
         x, sg, e = _as_host(pubkeys_x, self.nb), _as_host(sig_rs, 2 * self.nb), _as_host(challenges, self.nb)
@@ -835,6 +845,63 @@ class Curve:
         self.ctx.check(self.ctx.lib.ecgpu_ecdsa_recover_msg_batch(self.ctx.handle, self.id, _ptr(rec)[0] if stride else None, stride, _ptr(lens)[0], _ptr(sg)[0],
                                                                   _ptr(rid)[0], _ptr(out)[0], _ptr(ok)[0], len(sg), HOST, fl))
         return out, ok
+
+    # --- DigestSigner / DigestVerifier / recover_from_digest: the message-level calls on a chosen digest of the field's size ---
+    def ecdsa_sign_digest(self, hash_id: int, secret_d, msgs: Sequence[bytes], extra=None, flags: Optional[int] = None):
+        """DigestSigner::sign_digest / sign_digest_recoverable (extra=None) / RandomizedDigestSigner (extra given) for a batch, the
+        messages hashed with hash_id on the device -> (sig_rs, recovery_id, ok).  The RFC 6979 nonce keeps the curve's own hash."""
+        d = _as_host(secret_d, self.nb)
+        x = None if extra is None else _as_host(extra, self.nb)
+        if len(d) != len(msgs) or (x is not None and len(x) != len(d)):
+            raise ValueError("key, message and additional-data batches differ in length")
+        rec, lens, stride = pack_messages_aligned(msgs)
+        sig, rid, ok = _host_out(len(d), 2 * self.nb), np.zeros(len(d), dtype=np.uint8), np.zeros(len(d), dtype=np.uint8)
+        fl = self.default_ecdsa_flags() if flags is None else flags
+        self.ctx.check(self.ctx.lib.ecgpu_ecdsa_sign_digest_batch(self.ctx.handle, self.id, hash_id, _ptr(d)[0], _ptr(rec)[0] if stride else None, stride,
+                                                                  _ptr(lens)[0], _ptr(x)[0], _ptr(sig)[0], _ptr(rid)[0], _ptr(ok)[0], len(d), HOST, fl))
+        return sig, rid, ok
+
+    def ecdsa_sign_digest_device(self, hash_id: int, d_secret, d_msgs, msg_stride: int, d_msg_len, d_extra, d_sig_rs, d_recid, d_ok, n: int,
+                                 flags: Optional[int] = None):
+        fl = self.default_ecdsa_flags() if flags is None else flags
+        self.ctx.check(self.ctx.lib.ecgpu_ecdsa_sign_digest_batch(self.ctx.handle, self.id, hash_id, _ptr(d_secret)[0], _ptr(d_msgs)[0], msg_stride,
+                                                                  _ptr(d_msg_len)[0], _ptr(d_extra)[0], _ptr(d_sig_rs)[0], _ptr(d_recid)[0], _ptr(d_ok)[0], n, DEVICE, fl))
+
+    def ecdsa_verify_digest(self, hash_id: int, msgs: Sequence[bytes], sig_rs, pubkeys_xy, flags: Optional[int] = None) -> np.ndarray:
+        """DigestVerifier::verify_digest for a batch -> ok"""
+        sg, q = _as_host(sig_rs, 2 * self.nb), _as_host(pubkeys_xy, 2 * self.nb)
+        if not (len(msgs) == len(sg) == len(q)):
+            raise ValueError("message, signature and public-key batches differ in length")
+        rec, lens, stride = pack_messages_aligned(msgs)
+        ok = np.zeros(len(sg), dtype=np.uint8)
+        fl = self.default_ecdsa_flags() if flags is None else flags
+        self.ctx.check(self.ctx.lib.ecgpu_ecdsa_verify_digest_batch(self.ctx.handle, self.id, hash_id, _ptr(rec)[0] if stride else None, stride, _ptr(lens)[0],
+                                                                    _ptr(sg)[0], _ptr(q)[0], _ptr(ok)[0], len(sg), HOST, fl))
+        return ok
+
+    def ecdsa_verify_digest_device(self, hash_id: int, d_msgs, msg_stride: int, d_msg_len, d_sig_rs, d_pubkeys_xy, d_ok, n: int, flags: Optional[int] = None):
+        fl = self.default_ecdsa_flags() if flags is None else flags
+        self.ctx.check(self.ctx.lib.ecgpu_ecdsa_verify_digest_batch(self.ctx.handle, self.id, hash_id, _ptr(d_msgs)[0], msg_stride, _ptr(d_msg_len)[0],
+                                                                    _ptr(d_sig_rs)[0], _ptr(d_pubkeys_xy)[0], _ptr(d_ok)[0], n, DEVICE, fl))
+
+    def ecdsa_recover_digest(self, hash_id: int, msgs: Sequence[bytes], sig_rs, recovery_id, flags: Optional[int] = None):
+        """VerifyingKey::recover_from_digest for a batch -> (pubkeys_xy, ok)"""
+        sg = _as_host(sig_rs, 2 * self.nb)
+        rid = np.ascontiguousarray(recovery_id, dtype=np.uint8).reshape(-1)
+        if not (len(msgs) == len(sg) == len(rid)):
+            raise ValueError("message, signature and recovery-id batches differ in length")
+        rec, lens, stride = pack_messages_aligned(msgs)
+        out, ok = _host_out(len(sg), 2 * self.nb), np.zeros(len(sg), dtype=np.uint8)
+        fl = self.default_ecdsa_flags() if flags is None else flags
+        self.ctx.check(self.ctx.lib.ecgpu_ecdsa_recover_digest_batch(self.ctx.handle, self.id, hash_id, _ptr(rec)[0] if stride else None, stride, _ptr(lens)[0],
+                                                                     _ptr(sg)[0], _ptr(rid)[0], _ptr(out)[0], _ptr(ok)[0], len(sg), HOST, fl))
+        return out, ok
+
+    def ecdsa_recover_digest_device(self, hash_id: int, d_msgs, msg_stride: int, d_msg_len, d_sig_rs, d_recid, d_pubkeys_xy, d_ok, n: int,
+                                    flags: Optional[int] = None):
+        fl = self.default_ecdsa_flags() if flags is None else flags
+        self.ctx.check(self.ctx.lib.ecgpu_ecdsa_recover_digest_batch(self.ctx.handle, self.id, hash_id, _ptr(d_msgs)[0], msg_stride, _ptr(d_msg_len)[0],
+                                                                     _ptr(d_sig_rs)[0], _ptr(d_recid)[0], _ptr(d_pubkeys_xy)[0], _ptr(d_ok)[0], n, DEVICE, fl))
 
     def schnorr_sign_msg(self, secret_keys, msgs: Sequence[bytes], aux_rands=None):
         """BIP340 Signer::try_sign (aux_rands=None: 32 zero bytes) / try_sign_with_rng over SHA256(msg) for a batch (secp256k1)

@@ -93,6 +93,33 @@ def recover_from_msg(curve: Curve, messages: Sequence[bytes], sigs_rs: Sequence[
     return curve.ecdsa_recover_msg(list(messages), b"".join(sigs_rs), np.array(list(recovery_ids), dtype=np.uint8), flags)
 
 
+def sign_digest(curve: Curve, hash_id: int, secret_keys: Sequence[bytes], messages: Sequence[bytes], extra: Sequence[bytes] | None = None, flags=None):
+    """DigestSigner::sign_digest / sign_digest_recoverable (extra=None) / RandomizedDigestSigner for a batch of messages hashed with
+    hash_id (ecgpu.KECCAK256: Keccak256::new_with_prefix(msg), the reference's Ethereum example) on the device
+    (ecgpu_ecdsa_sign_digest_batch) -> (sig_rs, recovery_id, ok).  The digest must be of the curve's field size."""
+    return curve.ecdsa_sign_digest(hash_id, b"".join(secret_keys), list(messages), None if extra is None else b"".join(extra), flags)
+
+
+def verify_digest(curve: Curve, hash_id: int, pubkeys_xy: Sequence[bytes], messages: Sequence[bytes], sigs_rs: Sequence[bytes], flags=None) -> np.ndarray:
+    """DigestVerifier::verify_digest for a batch of fixed-width r || s signatures (ecgpu_ecdsa_verify_digest_batch)"""
+    return curve.ecdsa_verify_digest(hash_id, list(messages), b"".join(sigs_rs), b"".join(pubkeys_xy), flags)
+
+
+def recover_digest(curve: Curve, hash_id: int, messages: Sequence[bytes], sigs_rs: Sequence[bytes], recovery_ids: Sequence[int], flags=None):
+    """VerifyingKey::recover_from_digest for a batch (ecgpu_ecdsa_recover_digest_batch) -> (pubkeys_xy, ok)"""
+    return curve.ecdsa_recover_digest(hash_id, list(messages), b"".join(sigs_rs), np.array(list(recovery_ids), dtype=np.uint8), flags)
+
+
+def eth_addresses(ctx, pubkeys_xy) -> np.ndarray:
+    """Ethereum addresses of secp256k1 public keys: the last 20 bytes of Keccak-256 over each 64-byte x || y (what a caller of
+    recovery wants) -> (n, 20).  It is ecgpu_digest_batch on the records as they lie, 64 bytes apart, and a slice."""
+    from . import HOST, KECCAK256, _as_host, _host_out, _ptr
+    q = _as_host(pubkeys_xy, 64)
+    out = _host_out(len(q), 32)
+    ctx.check(ctx.lib.ecgpu_digest_batch(ctx.handle, KECCAK256, _ptr(q)[0], 64, None, _ptr(out)[0], len(q), HOST))
+    return np.ascontiguousarray(out[:, 12:])
+
+
 ORDER = {
     K256: 0xFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFEBAAEDCE6AF48A03BBFD25E8CD0364141,
     P256: 0xFFFFFFFF00000000FFFFFFFFFFFFFFFFBCE6FAADA7179E84F3B9CAC2FC632551,

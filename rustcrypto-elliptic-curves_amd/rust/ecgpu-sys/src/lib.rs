@@ -49,6 +49,10 @@ pub const ECGPU_REDUCE_NONZERO: c_uint = 1;
 /// `ecgpu_hash`: the hash of `ecgpu_expand_message_xmd_batch`
 pub const ECGPU_SHA256: c_int = 0;
 pub const ECGPU_SHA384: c_int = 1;
+/// the sponge family: Keccak-256 (the `sha3` crate's `Keccak256`, not FIPS 202), SHA3-256, SHA3-384
+pub const ECGPU_KECCAK256: c_int = 16;
+pub const ECGPU_SHA3_256: c_int = 17;
+pub const ECGPU_SHA3_384: c_int = 18;
 /// `ecgpu_hash_to_curve_batch`: hash_from_bytes (two maps and their sum) / encode_from_bytes (one map)
 pub const ECGPU_H2C_RO: c_int = 0;
 pub const ECGPU_H2C_NU: c_int = 1;
@@ -160,6 +164,13 @@ extern "C" {
                                         pubkeys_xy: *const u8, ok: *mut u8, n: usize, mem: c_int, flags: c_uint) -> c_int;
     pub fn ecgpu_ecdsa_recover_msg_batch(ctx: *mut ecgpu_ctx, curve: c_int, msgs: *const u8, msg_stride: usize, msg_len: *const u32, sig_rs: *const u8,
                                          recovery_id: *const u8, pubkeys_xy: *mut u8, ok: *mut u8, n: usize, mem: c_int, flags: c_uint) -> c_int;
+    pub fn ecgpu_hash_bytes(hash: c_int) -> usize;
+    pub fn ecgpu_ecdsa_sign_digest_batch(ctx: *mut ecgpu_ctx, curve: c_int, hash: c_int, secret_d: *const u8, msgs: *const u8, msg_stride: usize, msg_len: *const u32,
+                                         extra: *const u8, sig_rs: *mut u8, recovery_id: *mut u8, ok: *mut u8, n: usize, mem: c_int, flags: c_uint) -> c_int;
+    pub fn ecgpu_ecdsa_verify_digest_batch(ctx: *mut ecgpu_ctx, curve: c_int, hash: c_int, msgs: *const u8, msg_stride: usize, msg_len: *const u32, sig_rs: *const u8,
+                                           pubkeys_xy: *const u8, ok: *mut u8, n: usize, mem: c_int, flags: c_uint) -> c_int;
+    pub fn ecgpu_ecdsa_recover_digest_batch(ctx: *mut ecgpu_ctx, curve: c_int, hash: c_int, msgs: *const u8, msg_stride: usize, msg_len: *const u32, sig_rs: *const u8,
+                                            recovery_id: *const u8, pubkeys_xy: *mut u8, ok: *mut u8, n: usize, mem: c_int, flags: c_uint) -> c_int;
     pub fn ecgpu_schnorr_sign_msg_batch(ctx: *mut ecgpu_ctx, curve: c_int, secret_keys: *const u8, msgs: *const u8, msg_stride: usize, msg_len: *const u32,
                                         aux_rand: *const u8, sig_rs: *mut u8, pubkeys_x: *mut u8, ok: *mut u8, n: usize, mem: c_int) -> c_int;
     pub fn ecgpu_schnorr_verify_msg_batch(ctx: *mut ecgpu_ctx, curve: c_int, pubkeys_x: *const u8, msgs: *const u8, msg_stride: usize, msg_len: *const u32,
@@ -490,11 +501,12 @@ impl Context {
         for (i, m) in msgs.iter().enumerate() { rec[i * stride..i * stride + m.len()].copy_from_slice(m); }
         (rec, msgs.iter().map(|m| m.len() as u32).collect(), stride)
     }
-    /// Digest::digest for a batch (hash: ECGPU_SHA256 | ECGPU_SHA384) -> 32 | 48 bytes per message
+    /// Digest::digest for a batch (hash: ECGPU_SHA256 | ECGPU_SHA384 | ECGPU_KECCAK256 | ECGPU_SHA3_256 | ECGPU_SHA3_384) -> 32 | 48 bytes per message
     pub fn digest(&self, hash: c_int, msgs: &[&[u8]]) -> Result<Vec<u8>, Error> {
-        Self::arg(hash == ECGPU_SHA256 || hash == ECGPU_SHA384)?;
+        let db = unsafe { ecgpu_hash_bytes(hash) };
+        Self::arg(db != 0)?;
         let (rec, lens, stride) = Self::pack_messages_aligned(msgs);
-        let mut out = vec![0u8; (if hash == ECGPU_SHA384 { 48 } else { 32 }) * msgs.len()];
+        let mut out = vec![0u8; db * msgs.len()];
         self.check(unsafe { ecgpu_digest_batch(self.0, hash, rec.as_ptr(), stride, lens.as_ptr(), out.as_mut_ptr(), msgs.len(), ECGPU_MEM_HOST) })?;
         Ok(out)
     }
@@ -534,6 +546,46 @@ impl Context {
         self.check(unsafe {
             ecgpu_ecdsa_recover_msg_batch(self.0, curve, rec.as_ptr(), stride, lens.as_ptr(), sig_rs.as_ptr(), recovery_id.as_ptr(), xy.as_mut_ptr(), ok.as_mut_ptr(), n,
                                           ECGPU_MEM_HOST, flags)
+        })?;
+        Ok((xy, ok))
+    }
+    /// `DigestSigner::sign_digest` / `sign_digest_recoverable` (`extra = None`) / `RandomizedDigestSigner` (`extra` given) for a batch
+    /// of messages hashed on the device with `hash`, whose digest must be of the curve's field size (`D: Digest<OutputSize =
+    /// FieldBytesSize<C>>`); the RFC 6979 nonce keeps the curve's own hash -> (r || s, recovery ids, ok flags)
+    pub fn ecdsa_sign_digest(&self, curve: c_int, hash: c_int, secret_d: &[u8], msgs: &[&[u8]], extra: Option<&[u8]>, flags: c_uint) -> Result<(Vec<u8>, Vec<u8>, Vec<u8>), Error> {
+        let nb = Self::field_bytes(curve);
+        Self::arg(nb != 0 && secret_d.len() == nb * msgs.len() && extra.map_or(true, |e| e.len() == secret_d.len()))?;
+        let n = msgs.len();
+        let (rec, lens, stride) = Self::pack_messages_aligned(msgs);
+        let (mut sig, mut rid, mut ok) = (vec![0u8; 2 * nb * n], vec![0u8; n], vec![0u8; n]);
+        self.check(unsafe {
+            ecgpu_ecdsa_sign_digest_batch(self.0, curve, hash, secret_d.as_ptr(), rec.as_ptr(), stride, lens.as_ptr(), extra.map_or(core::ptr::null(), |e| e.as_ptr()),
+                                          sig.as_mut_ptr(), rid.as_mut_ptr(), ok.as_mut_ptr(), n, ECGPU_MEM_HOST, flags)
+        })?;
+        Ok((sig, rid, ok))
+    }
+    /// `DigestVerifier::verify_digest` for a batch of messages hashed with `hash` -> ok flags
+    pub fn ecdsa_verify_digest(&self, curve: c_int, hash: c_int, msgs: &[&[u8]], sig_rs: &[u8], pubkeys_xy: &[u8], flags: c_uint) -> Result<Vec<u8>, Error> {
+        let nb = Self::field_bytes(curve);
+        Self::arg(nb != 0 && sig_rs.len() == 2 * nb * msgs.len() && pubkeys_xy.len() == sig_rs.len())?;
+        let (rec, lens, stride) = Self::pack_messages_aligned(msgs);
+        let mut ok = vec![0u8; msgs.len()];
+        self.check(unsafe {
+            ecgpu_ecdsa_verify_digest_batch(self.0, curve, hash, rec.as_ptr(), stride, lens.as_ptr(), sig_rs.as_ptr(), pubkeys_xy.as_ptr(), ok.as_mut_ptr(), msgs.len(),
+                                            ECGPU_MEM_HOST, flags)
+        })?;
+        Ok(ok)
+    }
+    /// `VerifyingKey::recover_from_digest` for a batch of messages hashed with `hash` -> (x || y, ok flags)
+    pub fn ecdsa_recover_digest(&self, curve: c_int, hash: c_int, msgs: &[&[u8]], sig_rs: &[u8], recovery_id: &[u8], flags: c_uint) -> Result<(Vec<u8>, Vec<u8>), Error> {
+        let nb = Self::field_bytes(curve);
+        Self::arg(nb != 0 && sig_rs.len() == 2 * nb * msgs.len() && recovery_id.len() == msgs.len())?;
+        let n = msgs.len();
+        let (rec, lens, stride) = Self::pack_messages_aligned(msgs);
+        let (mut xy, mut ok) = (vec![0u8; 2 * nb * n], vec![0u8; n]);
+        self.check(unsafe {
+            ecgpu_ecdsa_recover_digest_batch(self.0, curve, hash, rec.as_ptr(), stride, lens.as_ptr(), sig_rs.as_ptr(), recovery_id.as_ptr(), xy.as_mut_ptr(), ok.as_mut_ptr(), n,
+                                             ECGPU_MEM_HOST, flags)
         })?;
         Ok((xy, ok))
     }

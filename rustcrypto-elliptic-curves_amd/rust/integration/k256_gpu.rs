@@ -198,6 +198,28 @@ pub fn ecdsa_recover_from_msg_batch(gpu: &Context, msgs: &[&[u8]], sigs: &[[u8; 
     let (xy, ok) = gpu.ecdsa_recover_msg(ECGPU_K256, msgs, &sigs.concat(), recovery_ids, ecgpu_sys::ECGPU_ECDSA_LOW_S)?;
     Ok(xy.chunks_exact(64).zip(ok.iter()).map(|(p, k)| if *k != 0 { Some(p.try_into().unwrap()) } else { None }).collect())
 }
+/// The Ethereum shape of ecdsa.rs:84-143 for a batch, `signing_key.sign_digest_recoverable(Keccak256::new_with_prefix(msg))`: Keccak-256
+/// of each message runs on the device, the RFC 6979 nonce stays on HMAC-SHA-256.  `added`: the additional data of
+/// `RandomizedDigestSigner::sign_digest_with_rng`.  -> (signature, recovery id)
+pub fn ecdsa_sign_keccak256_batch(gpu: &Context, keys: &[Scalar], msgs: &[&[u8]], added: Option<&[[u8; 32]]>) -> Result<Vec<Option<([u8; 64], u8)>>, Error> {
+    assert!(keys.len() == msgs.len() && added.map_or(true, |a| a.len() == keys.len()));
+    let ad = added.map(|a| a.concat());
+    let (sig, rec, ok) = gpu.ecdsa_sign_digest(ECGPU_K256, ecgpu_sys::ECGPU_KECCAK256, &put_scalars(keys.iter()), msgs, ad.as_deref(), ecgpu_sys::ECGPU_ECDSA_LOW_S)?;
+    Ok(sig.chunks_exact(64).zip(rec.iter().zip(ok.iter())).map(|(s, (r, k))| if *k != 0 { Some((s.try_into().unwrap(), *r)) } else { None }).collect())
+}
+/// `verifying_key.verify_digest(Keccak256::new_with_prefix(msg), &sig)` for many (message, r || s, x || y) triples
+pub fn ecdsa_verify_keccak256_batch(gpu: &Context, msgs: &[&[u8]], sigs: &[[u8; 64]], pubkeys_xy: &[[u8; 64]]) -> Result<Vec<bool>, Error> {
+    assert!(msgs.len() == sigs.len() && sigs.len() == pubkeys_xy.len());
+    let ok = gpu.ecdsa_verify_digest(ECGPU_K256, ecgpu_sys::ECGPU_KECCAK256, msgs, &sigs.concat(), &pubkeys_xy.concat(), ecgpu_sys::ECGPU_ECDSA_LOW_S)?;
+    Ok(ok.into_iter().map(|f| f != 0).collect())
+}
+/// `VerifyingKey::recover_from_digest(Keccak256::new_with_prefix(msg), &sig, recid)` (ecdsa.rs:111-143) -> x || y of each key, None
+/// where the reference returns Err.  The Ethereum address of a key is the last 20 bytes of `Context::digest(ECGPU_KECCAK256, ..)` over x || y.
+pub fn ecdsa_recover_keccak256_batch(gpu: &Context, msgs: &[&[u8]], sigs: &[[u8; 64]], recovery_ids: &[u8]) -> Result<Vec<Option<[u8; 64]>>, Error> {
+    assert!(msgs.len() == sigs.len() && sigs.len() == recovery_ids.len());
+    let (xy, ok) = gpu.ecdsa_recover_digest(ECGPU_K256, ecgpu_sys::ECGPU_KECCAK256, msgs, &sigs.concat(), recovery_ids, ecgpu_sys::ECGPU_ECDSA_LOW_S)?;
+    Ok(xy.chunks_exact(64).zip(ok.iter()).map(|(p, k)| if *k != 0 { Some(p.try_into().unwrap()) } else { None }).collect())
+}
 /// `Signer<Signature>::try_sign` of `schnorr::SigningKey` (schnorr/signing.rs:214-218; `aux_rands = None`: the reference's
 /// `Default::default()`) / `RandomizedSigner::try_sign_with_rng`: BIP340 over SHA256(msg), the digest computed on the device too.
 pub fn schnorr_sign_batch(gpu: &Context, secret_keys: &[[u8; 32]], msgs: &[&[u8]], aux_rands: Option<&[[u8; 32]]>) -> Result<Vec<Option<([u8; 64], [u8; 32])>>, Error> {
