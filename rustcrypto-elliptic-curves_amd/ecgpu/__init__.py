@@ -7,6 +7,10 @@ reference: `Curve.mul_by_generator` (MulByGenerator), `Curve.mul` (`&P * &k`), `
 (BatchNormalize), `Curve.field_*` (FieldElement).  The Rust shim that a maintainer would add is
 in ../rust/ (source only) and described in INTEGRATION.md.
 
+The boundary is written down once: `_PROTOTYPES` has one row per symbol of the header (checked against it, type class by type
+class, by tests/test_abi_load.py), and every wrapper enters the library through `_call` (the position of every argument of every
+wrapper is pinned by tests/test_binding_calls_cpu.py).  A new entry point is its table row and its wrapper.
+
 There is no CPU fallback: if libecgpu.so is missing or no gfx950 device is present, every entry
 point raises `EcgpuError`.
 """
@@ -51,6 +55,96 @@ _PKG_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB_PATH = os.environ.get("ECGPU_LIB") or os.path.join(_PKG_ROOT, "lib", "libecgpu.so")
 
 
+# symbol -> (restype, argtypes): one row per prototype of include/ecgpu.h, in the header's order
+vp, sz, i, u8p = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_void_p
+u, i64, u64, cstr = ctypes.c_uint, ctypes.c_int64, ctypes.c_uint64, ctypes.c_char_p
+pp, szp, ip = ctypes.POINTER(vp), ctypes.POINTER(sz), ctypes.POINTER(i)
+_PROTOTYPES = {
+    "ecgpu_create": (i, (pp, i)),
+    "ecgpu_destroy": (None, (vp,)),
+    "ecgpu_set_stream": (i, (vp, vp)),
+    "ecgpu_use_own_stream": (i, (vp,)),
+    "ecgpu_synchronize": (i, (vp,)),
+    "ecgpu_last_error": (cstr, (vp,)),
+    "ecgpu_last_error_copy": (i, (vp, cstr, sz)),
+    "ecgpu_set_option": (i, (vp, i, i64)),
+    "ecgpu_get_option": (i, (vp, i, ctypes.POINTER(i64))),
+    "ecgpu_fb_table_bytes": (i, (vp, i, szp, ip)),
+    "ecgpu_version": (cstr, ()),
+    "ecgpu_field_bytes": (sz, (i,)),
+    "ecgpu_host_alloc": (i, (vp, sz, pp)),
+    "ecgpu_host_free": (i, (vp, vp)),
+    "ecgpu_host_chunk_schedule": (i, (sz, sz, szp, sz)),
+    "ecgpu_debug_workspace": (i, (vp, i, vp, sz, szp)),
+    "ecgpu_timer_start": (i, (vp,)),
+    "ecgpu_timer_stop": (i, (vp, ctypes.POINTER(ctypes.c_float))),
+    "ecgpu_field_op_batch": (i, (vp, i, i, u8p, u8p, u8p, sz, i)),
+    "ecgpu_scalar_op_batch": (i, (vp, i, i, u8p, u8p, u8p, u8p, sz, i)),
+    "ecgpu_scalar_reduce_batch": (i, (vp, i, u8p, sz, u8p, sz, i, u)),
+    "ecgpu_point_add_batch": (i, (vp, i, u8p, u8p, u8p, sz, i)),
+    "ecgpu_point_add_mixed_batch": (i, (vp, i, u8p, u8p, u8p, sz, i)),
+    "ecgpu_point_double_batch": (i, (vp, i, u8p, u8p, sz, i)),
+    "ecgpu_point_eq_batch": (i, (vp, i, u8p, u8p, u8p, sz, i)),
+    "ecgpu_batch_normalize": (i, (vp, i, u8p, u8p, u8p, sz, i)),
+    "ecgpu_mul_batch": (i, (vp, i, u8p, u8p, i, u8p, i, u8p, sz, i, u)),
+    "ecgpu_mul_batch_checked": (i, (vp, i, u8p, u8p, i, u8p, i, u8p, u8p, sz, i, u)),
+    "ecgpu_lincomb_batch": (i, (vp, i, u8p, u8p, i, sz, u8p, i, u8p, sz, i, u)),
+    "ecgpu_lincomb_batch_checked": (i, (vp, i, u8p, u8p, i, sz, u8p, i, u8p, u8p, sz, i, u)),
+    "ecgpu_msm": (i, (vp, i, u8p, u8p, i, sz, u8p, i, i)),
+    "ecgpu_validate_scalars": (i, (vp, i, u8p, u8p, sz, i)),
+    "ecgpu_validate_points": (i, (vp, i, u8p, u8p, sz, i)),
+    "ecgpu_decompress_batch": (i, (vp, i, u8p, u8p, u8p, u8p, sz, i)),
+    "ecgpu_to_bytes_batch": (i, (vp, i, u8p, i, u8p, sz, i)),
+    "ecgpu_from_bytes_batch": (i, (vp, i, u8p, u8p, u8p, sz, i)),
+    "ecgpu_sec1_encode_batch": (i, (vp, i, u8p, i, i, u8p, sz, i)),
+    "ecgpu_sec1_decode_batch": (i, (vp, i, u8p, sz, u8p, u8p, sz, i)),
+    "ecgpu_ecdsa_verify_batch": (i, (vp, i, u8p, u8p, u8p, u8p, sz, i, u)),
+    "ecgpu_ecdsa_sign_batch": (i, (vp, i, u8p, u8p, u8p, u8p, u8p, u8p, sz, i, u)),
+    "ecgpu_rfc6979_nonce_batch": (i, (vp, i, u8p, u8p, u8p, u8p, sz, i)),
+    "ecgpu_ecdsa_sign_prehash_batch": (i, (vp, i, u8p, u8p, u8p, u8p, u8p, u8p, sz, i, u)),
+    "ecgpu_ecdsa_recover_batch": (i, (vp, i, u8p, u8p, u8p, u8p, u8p, sz, i, u)),
+    "ecgpu_ecdh_batch": (i, (vp, i, u8p, u8p, u8p, u8p, sz, i)),
+    "ecgpu_schnorr_verify_batch": (i, (vp, i, u8p, u8p, u8p, u8p, sz, i)),
+    "ecgpu_schnorr_verify_prehash_batch": (i, (vp, i, u8p, u8p, u8p, u8p, sz, i)),
+    "ecgpu_schnorr_sign_prehash_batch": (i, (vp, i, u8p, u8p, u8p, u8p, u8p, u8p, sz, i)),
+    "ecgpu_map_to_curve_batch": (i, (vp, i, u8p, i, u8p, u8p, sz, i)),
+    "ecgpu_hash_bytes": (sz, (i,)),
+    "ecgpu_expand_message_xmd_batch": (i, (vp, i, u8p, sz, u8p, u8p, sz, u8p, sz, sz, i)),
+    "ecgpu_field_from_okm_batch": (i, (vp, i, u8p, u8p, sz, i)),
+    "ecgpu_hash_to_curve_batch": (i, (vp, i, u8p, sz, u8p, u8p, sz, i, u8p, u8p, sz, i)),
+    "ecgpu_hash_to_scalar_batch": (i, (vp, i, u8p, sz, u8p, u8p, sz, u8p, sz, i)),
+    "ecgpu_digest_batch": (i, (vp, i, u8p, sz, u8p, u8p, sz, i)),
+    "ecgpu_ecdsa_sign_msg_batch": (i, (vp, i, u8p, u8p, sz, u8p, u8p, u8p, u8p, u8p, sz, i, u)),
+    "ecgpu_ecdsa_verify_msg_batch": (i, (vp, i, u8p, sz, u8p, u8p, u8p, u8p, sz, i, u)),
+    "ecgpu_ecdsa_recover_msg_batch": (i, (vp, i, u8p, sz, u8p, u8p, u8p, u8p, u8p, sz, i, u)),
+    "ecgpu_ecdsa_sign_digest_batch": (i, (vp, i, i, u8p, u8p, sz, u8p, u8p, u8p, u8p, u8p, sz, i, u)),
+    "ecgpu_ecdsa_verify_digest_batch": (i, (vp, i, i, u8p, sz, u8p, u8p, u8p, u8p, sz, i, u)),
+    "ecgpu_ecdsa_recover_digest_batch": (i, (vp, i, i, u8p, sz, u8p, u8p, u8p, u8p, u8p, sz, i, u)),
+    "ecgpu_schnorr_sign_msg_batch": (i, (vp, i, u8p, u8p, sz, u8p, u8p, u8p, u8p, u8p, sz, i)),
+    "ecgpu_schnorr_verify_msg_batch": (i, (vp, i, u8p, u8p, sz, u8p, u8p, u8p, sz, i)),
+    "ecgpu_schnorr_batch_verify": (i, (vp, i, u8p, u8p, u8p, u8p, u8p, ip, sz, i, u)),
+    "ecgpu_schnorr_batch_verify_prehash": (i, (vp, i, u8p, u8p, u8p, u8p, u8p, ip, sz, i, u)),
+    "ecgpu_schnorr_batch_verify_msg": (i, (vp, i, u8p, u8p, sz, u8p, u8p, u8p, u8p, ip, sz, i, u)),
+    "ecgpu_group_create": (i, (pp, ip, i, u)),
+    "ecgpu_group_destroy": (None, (vp,)),
+    "ecgpu_group_size": (i, (vp,)),
+    "ecgpu_group_context": (vp, (vp, i)),
+    "ecgpu_group_last_error": (cstr, (vp,)),
+    "ecgpu_group_gather_path": (cstr, (vp,)),
+    "ecgpu_group_synchronize": (i, (vp,)),
+    "ecgpu_shard_range": (i, (sz, i, i, szp, szp)),
+    "ecgpu_group_mul_batch": (i, (vp, i, u8p, u8p, i, u8p, i, u8p, sz, u)),
+    "ecgpu_group_lincomb_batch": (i, (vp, i, u8p, u8p, i, sz, u8p, i, u8p, sz, u)),
+    "ecgpu_group_lincomb_sharded": (i, (vp, i, pp, pp, i, sz, pp, i, pp, szp, u)),
+    "ecgpu_group_msm": (i, (vp, i, u8p, u8p, i, sz, u8p, i)),
+    "ecgpu_group_msm_sharded": (i, (vp, i, pp, pp, i, szp, u8p, i)),
+    "ecgpu_synth_scalars": (i, (vp, i, u64, u64, u8p, sz)),
+    "ecgpu_synth_points": (i, (vp, i, u64, u64, u8p, sz)),
+}
+del vp, sz, i, u8p, u, i64, u64, cstr, pp, szp, ip
+EXPORTED_SYMBOLS = tuple(_PROTOTYPES)
+
+
 def host_chunk_schedule(n: int, pass_units: int) -> list:
     """chunk sizes of a host-buffer batch (ecgpu_host_chunk_schedule; no device needed)"""
     lib = load_library()
@@ -85,139 +179,12 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
     if not os.path.exists(p):
         raise EcgpuError(f"{p} not found: build it with `make -C rustcrypto-elliptic-curves_amd` (no CPU fallback exists)")
     lib = ctypes.CDLL(p)
-    vp, sz, i, u8p = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_void_p
-    lib.ecgpu_create.argtypes = [ctypes.POINTER(vp), i]
-    lib.ecgpu_destroy.argtypes = [vp]
-    lib.ecgpu_destroy.restype = None
-    lib.ecgpu_set_stream.argtypes = [vp, vp]
-    lib.ecgpu_use_own_stream.argtypes = [vp]
-    lib.ecgpu_last_error_copy.argtypes = [vp, ctypes.c_char_p, sz]
-    lib.ecgpu_set_option.argtypes = [vp, i, ctypes.c_int64]
-    lib.ecgpu_get_option.argtypes = [vp, i, ctypes.POINTER(ctypes.c_int64)]
-    lib.ecgpu_fb_table_bytes.argtypes = [vp, i, ctypes.POINTER(sz), ctypes.POINTER(i)]
-    lib.ecgpu_ecdh_batch.argtypes = [vp, i, u8p, u8p, u8p, u8p, sz, i]
-    lib.ecgpu_sec1_encode_batch.argtypes = [vp, i, u8p, i, i, u8p, sz, i]
-    lib.ecgpu_sec1_decode_batch.argtypes = [vp, i, u8p, sz, u8p, u8p, sz, i]
-    lib.ecgpu_synchronize.argtypes = [vp]
-    lib.ecgpu_last_error.argtypes = [vp]
-    lib.ecgpu_last_error.restype = ctypes.c_char_p
-    lib.ecgpu_version.restype = ctypes.c_char_p
-    lib.ecgpu_field_bytes.argtypes = [i]
-    lib.ecgpu_field_bytes.restype = sz
-    lib.ecgpu_hash_bytes.argtypes = [i]
-    lib.ecgpu_hash_bytes.restype = sz
-    lib.ecgpu_host_alloc.argtypes = [vp, sz, ctypes.POINTER(vp)]
-    lib.ecgpu_host_free.argtypes = [vp, vp]
-    lib.ecgpu_debug_workspace.argtypes = [vp, i, vp, sz, ctypes.POINTER(sz)]
-    lib.ecgpu_host_chunk_schedule.argtypes = [sz, sz, ctypes.POINTER(sz), sz]
-    pp = ctypes.POINTER(vp)
-    lib.ecgpu_group_create.argtypes = [ctypes.POINTER(vp), ctypes.POINTER(i), i, ctypes.c_uint]
-    lib.ecgpu_group_destroy.argtypes = [vp]
-    lib.ecgpu_group_destroy.restype = None
-    lib.ecgpu_group_size.argtypes = [vp]
-    lib.ecgpu_group_context.argtypes = [vp, i]
-    lib.ecgpu_group_context.restype = vp
-    lib.ecgpu_group_last_error.argtypes = [vp]
-    lib.ecgpu_group_last_error.restype = ctypes.c_char_p
-    lib.ecgpu_group_gather_path.argtypes = [vp]
-    lib.ecgpu_group_gather_path.restype = ctypes.c_char_p
-    lib.ecgpu_group_synchronize.argtypes = [vp]
-    lib.ecgpu_shard_range.argtypes = [sz, i, i, ctypes.POINTER(sz), ctypes.POINTER(sz)]
-    lib.ecgpu_group_mul_batch.argtypes = [vp, i, u8p, u8p, i, u8p, i, u8p, sz, ctypes.c_uint]
-    lib.ecgpu_group_lincomb_batch.argtypes = [vp, i, u8p, u8p, i, sz, u8p, i, u8p, sz, ctypes.c_uint]
-    lib.ecgpu_group_lincomb_sharded.argtypes = [vp, i, pp, pp, i, sz, pp, i, pp, ctypes.POINTER(sz), ctypes.c_uint]
-    lib.ecgpu_group_msm.argtypes = [vp, i, u8p, u8p, i, sz, u8p, i]
-    lib.ecgpu_group_msm_sharded.argtypes = [vp, i, pp, pp, i, ctypes.POINTER(sz), u8p, i]
-    lib.ecgpu_timer_start.argtypes = [vp]
-    lib.ecgpu_timer_stop.argtypes = [vp, ctypes.POINTER(ctypes.c_float)]
-    lib.ecgpu_field_op_batch.argtypes = [vp, i, i, u8p, u8p, u8p, sz, i]
-    lib.ecgpu_scalar_op_batch.argtypes = [vp, i, i, u8p, u8p, u8p, u8p, sz, i]
-    lib.ecgpu_scalar_reduce_batch.argtypes = [vp, i, u8p, sz, u8p, sz, i, ctypes.c_uint]
-    lib.ecgpu_point_add_batch.argtypes = [vp, i, u8p, u8p, u8p, sz, i]
-    lib.ecgpu_point_add_mixed_batch.argtypes = [vp, i, u8p, u8p, u8p, sz, i]
-    lib.ecgpu_point_double_batch.argtypes = [vp, i, u8p, u8p, sz, i]
-    lib.ecgpu_batch_normalize.argtypes = [vp, i, u8p, u8p, u8p, sz, i]
-    lib.ecgpu_point_eq_batch.argtypes = [vp, i, u8p, u8p, u8p, sz, i]
-    lib.ecgpu_mul_batch_checked.argtypes = [vp, i, u8p, u8p, i, u8p, i, u8p, u8p, sz, i, ctypes.c_uint]
-    lib.ecgpu_lincomb_batch_checked.argtypes = [vp, i, u8p, u8p, i, sz, u8p, i, u8p, u8p, sz, i, ctypes.c_uint]
-    lib.ecgpu_mul_batch.argtypes = [vp, i, u8p, u8p, i, u8p, i, u8p, sz, i, ctypes.c_uint]
-    lib.ecgpu_lincomb_batch.argtypes = [vp, i, u8p, u8p, i, sz, u8p, i, u8p, sz, i, ctypes.c_uint]
-    lib.ecgpu_msm.argtypes = [vp, i, u8p, u8p, i, sz, u8p, i, i]
-    lib.ecgpu_validate_scalars.argtypes = [vp, i, u8p, u8p, sz, i]
-    lib.ecgpu_validate_points.argtypes = [vp, i, u8p, u8p, sz, i]
-    lib.ecgpu_decompress_batch.argtypes = [vp, i, u8p, u8p, u8p, u8p, sz, i]
-    lib.ecgpu_to_bytes_batch.argtypes = [vp, i, u8p, i, u8p, sz, i]
-    lib.ecgpu_from_bytes_batch.argtypes = [vp, i, u8p, u8p, u8p, sz, i]
-    lib.ecgpu_ecdsa_verify_batch.argtypes = [vp, i, u8p, u8p, u8p, u8p, sz, i, ctypes.c_uint]
-    lib.ecgpu_map_to_curve_batch.argtypes = [vp, i, u8p, i, u8p, u8p, sz, i]
-    lib.ecgpu_ecdsa_recover_batch.argtypes = [vp, i, u8p, u8p, u8p, u8p, u8p, sz, i, ctypes.c_uint]
-    lib.ecgpu_schnorr_verify_batch.argtypes = [vp, i, u8p, u8p, u8p, u8p, sz, i]
-    lib.ecgpu_schnorr_verify_prehash_batch.argtypes = [vp, i, u8p, u8p, u8p, u8p, sz, i]
-    lib.ecgpu_expand_message_xmd_batch.argtypes = [vp, i, u8p, sz, u8p, u8p, sz, u8p, sz, sz, i]
-    lib.ecgpu_field_from_okm_batch.argtypes = [vp, i, u8p, u8p, sz, i]
-    lib.ecgpu_hash_to_curve_batch.argtypes = [vp, i, u8p, sz, u8p, u8p, sz, i, u8p, u8p, sz, i]
-    lib.ecgpu_hash_to_scalar_batch.argtypes = [vp, i, u8p, sz, u8p, u8p, sz, u8p, sz, i]
-    lib.ecgpu_ecdsa_sign_batch.argtypes = [vp, i, u8p, u8p, u8p, u8p, u8p, u8p, sz, i, ctypes.c_uint]
-    lib.ecgpu_rfc6979_nonce_batch.argtypes = [vp, i, u8p, u8p, u8p, u8p, sz, i]
-    lib.ecgpu_ecdsa_sign_prehash_batch.argtypes = [vp, i, u8p, u8p, u8p, u8p, u8p, u8p, sz, i, ctypes.c_uint]
-    lib.ecgpu_schnorr_sign_prehash_batch.argtypes = [vp, i, u8p, u8p, u8p, u8p, u8p, u8p, sz, i]
-    lib.ecgpu_digest_batch.argtypes = [vp, i, u8p, sz, u8p, u8p, sz, i]
-    lib.ecgpu_ecdsa_sign_msg_batch.argtypes = [vp, i, u8p, u8p, sz, u8p, u8p, u8p, u8p, u8p, sz, i, ctypes.c_uint]
-    lib.ecgpu_ecdsa_verify_msg_batch.argtypes = [vp, i, u8p, sz, u8p, u8p, u8p, u8p, sz, i, ctypes.c_uint]
-    lib.ecgpu_ecdsa_recover_msg_batch.argtypes = [vp, i, u8p, sz, u8p, u8p, u8p, u8p, u8p, sz, i, ctypes.c_uint]
-    lib.ecgpu_ecdsa_sign_digest_batch.argtypes = [vp, i, i, u8p, u8p, sz, u8p, u8p, u8p, u8p, u8p, sz, i, ctypes.c_uint]
-    lib.ecgpu_ecdsa_verify_digest_batch.argtypes = [vp, i, i, u8p, sz, u8p, u8p, u8p, u8p, sz, i, ctypes.c_uint]
-    lib.ecgpu_ecdsa_recover_digest_batch.argtypes = [vp, i, i, u8p, sz, u8p, u8p, u8p, u8p, u8p, sz, i, ctypes.c_uint]
-    lib.ecgpu_schnorr_sign_msg_batch.argtypes = [vp, i, u8p, u8p, sz, u8p, u8p, u8p, u8p, u8p, sz, i]
-    lib.ecgpu_schnorr_verify_msg_batch.argtypes = [vp, i, u8p, u8p, sz, u8p, u8p, u8p, sz, i]
-    lib.ecgpu_schnorr_batch_verify.argtypes = [vp, i, u8p, u8p, u8p, u8p, u8p, ctypes.POINTER(i), sz, i, ctypes.c_uint]
-    lib.ecgpu_schnorr_batch_verify_prehash.argtypes = [vp, i, u8p, u8p, u8p, u8p, u8p, ctypes.POINTER(i), sz, i, ctypes.c_uint]
-    lib.ecgpu_schnorr_batch_verify_msg.argtypes = [vp, i, u8p, u8p, sz, u8p, u8p, u8p, u8p, ctypes.POINTER(i), sz, i, ctypes.c_uint]
-    lib.ecgpu_synth_scalars.argtypes = [vp, i, ctypes.c_uint64, ctypes.c_uint64, u8p, sz]
-    lib.ecgpu_synth_points.argtypes = [vp, i, ctypes.c_uint64, ctypes.c_uint64, u8p, sz]
-    for name in ("ecgpu_create", "ecgpu_set_stream", "ecgpu_synchronize", "ecgpu_timer_start", "ecgpu_timer_stop",
-                 "ecgpu_field_op_batch", "ecgpu_scalar_op_batch", "ecgpu_scalar_reduce_batch", "ecgpu_point_add_batch", "ecgpu_point_add_mixed_batch",
-                 "ecgpu_point_double_batch", "ecgpu_batch_normalize", "ecgpu_mul_batch", "ecgpu_lincomb_batch",
-                 "ecgpu_msm", "ecgpu_validate_scalars", "ecgpu_validate_points", "ecgpu_decompress_batch",
-                 "ecgpu_synth_scalars", "ecgpu_synth_points", "ecgpu_point_eq_batch", "ecgpu_mul_batch_checked",
-                 "ecgpu_lincomb_batch_checked", "ecgpu_ecdsa_verify_batch", "ecgpu_ecdsa_sign_batch", "ecgpu_to_bytes_batch",
-                 "ecgpu_from_bytes_batch", "ecgpu_host_alloc", "ecgpu_host_free", "ecgpu_schnorr_verify_batch",
-                 "ecgpu_ecdsa_recover_batch", "ecgpu_map_to_curve_batch", "ecgpu_use_own_stream", "ecgpu_last_error_copy",
-                 "ecgpu_set_option", "ecgpu_get_option", "ecgpu_fb_table_bytes", "ecgpu_sec1_encode_batch", "ecgpu_sec1_decode_batch",
-                 "ecgpu_ecdh_batch", "ecgpu_debug_workspace", "ecgpu_host_chunk_schedule", "ecgpu_group_create", "ecgpu_group_size",
-                 "ecgpu_group_synchronize", "ecgpu_shard_range", "ecgpu_group_mul_batch", "ecgpu_group_lincomb_batch", "ecgpu_group_lincomb_sharded",
-                 "ecgpu_group_msm", "ecgpu_group_msm_sharded", "ecgpu_schnorr_verify_prehash_batch", "ecgpu_expand_message_xmd_batch",
-                 "ecgpu_field_from_okm_batch", "ecgpu_hash_to_curve_batch", "ecgpu_hash_to_scalar_batch", "ecgpu_rfc6979_nonce_batch",
-                 "ecgpu_ecdsa_sign_prehash_batch", "ecgpu_schnorr_sign_prehash_batch", "ecgpu_digest_batch", "ecgpu_ecdsa_sign_msg_batch",
-                 "ecgpu_ecdsa_verify_msg_batch", "ecgpu_ecdsa_recover_msg_batch", "ecgpu_schnorr_sign_msg_batch", "ecgpu_schnorr_verify_msg_batch",
-                 "ecgpu_schnorr_batch_verify", "ecgpu_schnorr_batch_verify_prehash", "ecgpu_schnorr_batch_verify_msg",
-                 "ecgpu_ecdsa_sign_digest_batch", "ecgpu_ecdsa_verify_digest_batch", "ecgpu_ecdsa_recover_digest_batch"):
-        getattr(lib, name).restype = ctypes.c_int
+    for name, (restype, argtypes) in _PROTOTYPES.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, list(argtypes)
     if path is None:
         _lib = lib
     return lib
-
-
-EXPORTED_SYMBOLS = (
-    "ecgpu_create", "ecgpu_destroy", "ecgpu_set_stream", "ecgpu_synchronize", "ecgpu_last_error", "ecgpu_version",
-    "ecgpu_field_bytes", "ecgpu_timer_start", "ecgpu_timer_stop", "ecgpu_field_op_batch", "ecgpu_scalar_op_batch", "ecgpu_scalar_reduce_batch", "ecgpu_point_add_batch",
-    "ecgpu_point_add_mixed_batch", "ecgpu_point_double_batch", "ecgpu_batch_normalize", "ecgpu_mul_batch",
-    "ecgpu_lincomb_batch", "ecgpu_msm", "ecgpu_validate_scalars", "ecgpu_validate_points", "ecgpu_decompress_batch",
-    "ecgpu_synth_scalars", "ecgpu_synth_points", "ecgpu_ecdsa_verify_batch", "ecgpu_ecdsa_sign_batch",
-    "ecgpu_to_bytes_batch", "ecgpu_from_bytes_batch", "ecgpu_host_alloc", "ecgpu_host_free", "ecgpu_schnorr_verify_batch", "ecgpu_ecdsa_recover_batch", "ecgpu_map_to_curve_batch",
-    "ecgpu_point_eq_batch", "ecgpu_mul_batch_checked", "ecgpu_lincomb_batch_checked",
-    "ecgpu_use_own_stream", "ecgpu_last_error_copy", "ecgpu_set_option", "ecgpu_get_option", "ecgpu_fb_table_bytes",
-    "ecgpu_sec1_encode_batch", "ecgpu_sec1_decode_batch", "ecgpu_ecdh_batch", "ecgpu_debug_workspace", "ecgpu_host_chunk_schedule",
-    "ecgpu_group_create", "ecgpu_group_destroy", "ecgpu_group_size", "ecgpu_group_context", "ecgpu_group_last_error", "ecgpu_group_gather_path",
-    "ecgpu_group_synchronize", "ecgpu_shard_range", "ecgpu_group_mul_batch", "ecgpu_group_lincomb_batch", "ecgpu_group_lincomb_sharded",
-    "ecgpu_group_msm", "ecgpu_group_msm_sharded",
-    "ecgpu_schnorr_verify_prehash_batch", "ecgpu_expand_message_xmd_batch", "ecgpu_field_from_okm_batch", "ecgpu_hash_to_curve_batch",
-    "ecgpu_hash_to_scalar_batch", "ecgpu_rfc6979_nonce_batch", "ecgpu_ecdsa_sign_prehash_batch", "ecgpu_schnorr_sign_prehash_batch",
-    "ecgpu_digest_batch", "ecgpu_ecdsa_sign_msg_batch", "ecgpu_ecdsa_verify_msg_batch", "ecgpu_ecdsa_recover_msg_batch",
-    "ecgpu_schnorr_sign_msg_batch", "ecgpu_schnorr_verify_msg_batch",
-    "ecgpu_schnorr_batch_verify", "ecgpu_schnorr_batch_verify_prehash", "ecgpu_schnorr_batch_verify_msg",
-    "ecgpu_hash_bytes", "ecgpu_ecdsa_sign_digest_batch", "ecgpu_ecdsa_verify_digest_batch", "ecgpu_ecdsa_recover_digest_batch",
-)
 
 
 def _ptr(x):
@@ -235,6 +202,43 @@ def _ptr(x):
             raise ValueError("the C ABI takes dense buffers: pass a contiguous tensor")
         return ctypes.c_void_p(x.data_ptr()), x
     raise TypeError(type(x))
+
+
+_AS_IS = (int, np.integer, ctypes._SimpleCData, ctypes.Array, type(ctypes.byref(ctypes.c_int())))
+
+
+def _call(owner, name: str, *args):
+    """The one path into the library: `owner` (a Context or a Group) gives the library, the handle that goes first and the
+    check of the status.  Integers (sizes, flags, raw device pointers; Python's or numpy's), None and ctypes objects pass as they
+    are, for ctypes to convert; everything else - numpy arrays, torch tensors - goes through _ptr and its checks.  `args` keeps
+    the arrays alive until the call has returned."""
+    owner.check(getattr(owner.lib, name)(owner.handle, *[a if a is None or isinstance(a, _AS_IS) else _ptr(a)[0] for a in args]))
+
+
+def _curve_id(curve) -> int:
+    return CURVE_IDS[curve] if isinstance(curve, str) else int(curve)
+
+
+def _point_bytes(fmt: int, nb: int) -> int:
+    return (3 if fmt == PROJECTIVE else 2) * nb
+
+
+def _equal_lengths(what: str, *batches):
+    """the batches of one call (arrays or message lists; None: an optional one that is absent) hold the same number of elements"""
+    if len({len(b) for b in batches if b is not None}) > 1:
+        raise ValueError(what + " batches differ in length")
+
+
+def _host_messages(msgs: Sequence[bytes], aligned: bool = True) -> tuple:
+    """the message arguments of a host batch: (records, or None where every message is empty; stride; lengths)"""
+    rec, lens, stride = pack_messages_aligned(msgs) if aligned else pack_messages(msgs)
+    return rec if stride else None, stride, lens
+
+
+def _host_dst(dst: bytes) -> tuple:
+    """(domain separation tag, or None for an empty one; its length)"""
+    d = np.frombuffer(bytes(dst), dtype=np.uint8)
+    return d if len(d) else None, len(d)
 
 
 class Context:
@@ -269,25 +273,24 @@ class Context:
 
     def set_stream(self, stream_handle: int):
         """All later launches go to this hipStream_t; 0 / None is the legacy default stream (PyTorch's default stream)."""
-        self.check(self.lib.ecgpu_set_stream(self.handle, ctypes.c_void_p(stream_handle or None)))
+        _call(self, "ecgpu_set_stream", ctypes.c_void_p(stream_handle or None))
 
     def use_own_stream(self):
         """Back to the context's own (blocking) stream."""
-        self.check(self.lib.ecgpu_use_own_stream(self.handle))
+        _call(self, "ecgpu_use_own_stream")
 
     def set_option(self, option: int, value: int):
-        self.check(self.lib.ecgpu_set_option(self.handle, option, value))
+        _call(self, "ecgpu_set_option", option, value)
 
     def get_option(self, option: int) -> int:
         v = ctypes.c_int64()
-        self.check(self.lib.ecgpu_get_option(self.handle, option, ctypes.byref(v)))
+        _call(self, "ecgpu_get_option", option, ctypes.byref(v))
         return v.value
 
     def fb_table_bytes(self, curve) -> tuple:
         """(bytes of device memory held by the curve's generator tables, widest window among them)"""
-        cid = CURVE_IDS[curve] if isinstance(curve, str) else int(curve)
         b, w = ctypes.c_size_t(), ctypes.c_int()
-        self.check(self.lib.ecgpu_fb_table_bytes(self.handle, cid, ctypes.byref(b), ctypes.byref(w)))
+        _call(self, "ecgpu_fb_table_bytes", _curve_id(curve), ctypes.byref(b), ctypes.byref(w))
         return b.value, w.value
 
     def last_error(self) -> str:
@@ -299,40 +302,44 @@ class Context:
         """contents of one of the context's device workspaces (ecgpu_debug_workspace): 0 table workspace, 1 ECDSA / ECDH
         intermediates, 2 MSM, 3 BIP340 challenges and message digests, 16 + i staging slot i (0 .. 27).  b"" if it does not exist yet."""
         b = ctypes.c_size_t()
-        self.check(self.lib.ecgpu_debug_workspace(self.handle, which, None, 0, ctypes.byref(b)))
+        _call(self, "ecgpu_debug_workspace", which, None, 0, ctypes.byref(b))
         if not b.value:
             return b""
         buf = np.empty(b.value, dtype=np.uint8)
-        self.check(self.lib.ecgpu_debug_workspace(self.handle, which, ctypes.c_void_p(buf.ctypes.data), b.value, ctypes.byref(b)))
+        _call(self, "ecgpu_debug_workspace", which, buf, b.value, ctypes.byref(b))
         return buf.tobytes()
 
     def synchronize(self):
-        self.check(self.lib.ecgpu_synchronize(self.handle))
+        _call(self, "ecgpu_synchronize")
 
     def pinned_array(self, shape, dtype=np.uint8) -> np.ndarray:
         """numpy array over page-locked host memory (ecgpu_host_alloc); freed with the context."""
         nbytes = int(np.prod(shape)) * np.dtype(dtype).itemsize
         p = ctypes.c_void_p()
-        self.check(self.lib.ecgpu_host_alloc(self.handle, nbytes, ctypes.byref(p)))
+        _call(self, "ecgpu_host_alloc", nbytes, ctypes.byref(p))
         self._pinned.append(p)
         buf = (ctypes.c_uint8 * max(nbytes, 1)).from_address(p.value)
         return np.frombuffer(buf, dtype=dtype, count=int(np.prod(shape))).reshape(shape)
 
     def timer_start(self):
-        self.check(self.lib.ecgpu_timer_start(self.handle))
+        _call(self, "ecgpu_timer_start")
 
     def timer_stop(self) -> float:
         ms = ctypes.c_float()
-        self.check(self.lib.ecgpu_timer_stop(self.handle, ctypes.byref(ms)))
+        _call(self, "ecgpu_timer_stop", ctypes.byref(ms))
         return ms.value
 
     def curve(self, name_or_id) -> "Curve":
-        cid = CURVE_IDS[name_or_id] if isinstance(name_or_id, str) else int(name_or_id)
-        return Curve(self, cid)
+        return Curve(self, _curve_id(name_or_id))
 
 
 def _host_out(n: int, width: int) -> np.ndarray:
     return np.zeros((n, width), dtype=np.uint8)
+
+
+def _host_flags(n: int) -> np.ndarray:
+    """one byte per element: ok / inf / eq / recovery id"""
+    return np.zeros(n, dtype=np.uint8)
 
 
 def _as_host(x, width: int) -> np.ndarray:
@@ -369,24 +376,22 @@ def pack_messages_aligned(msgs: Sequence[bytes]):
 
 def digest(ctx: "Context", hash_id: int, msgs: Sequence[bytes]) -> np.ndarray:
     """SHA-256 / SHA-384 / Keccak-256 / SHA3-256 / SHA3-384 of every message on the device -> (n, 32 | 48) digests (ecgpu_digest_batch)"""
-    rec, lens, stride = pack_messages_aligned(msgs)
+    m = _host_messages(msgs)
     out = _host_out(len(msgs), DIGEST_BYTES.get(hash_id, 48))
-    ctx.check(ctx.lib.ecgpu_digest_batch(ctx.handle, hash_id, _ptr(rec)[0] if stride else None, stride, _ptr(lens)[0], _ptr(out)[0], len(msgs), HOST))
+    _call(ctx, "ecgpu_digest_batch", hash_id, *m, out, len(msgs), HOST)
     return out
 
 
 def digest_device(ctx: "Context", hash_id: int, d_msgs, msg_stride: int, d_msg_len, d_out, n: int):
     """the same over device buffers (d_msg_len may be None: every message is msg_stride bytes; d_out 4-byte aligned)"""
-    ctx.check(ctx.lib.ecgpu_digest_batch(ctx.handle, hash_id, _ptr(d_msgs)[0], msg_stride, _ptr(d_msg_len)[0], _ptr(d_out)[0], n, DEVICE))
+    _call(ctx, "ecgpu_digest_batch", hash_id, d_msgs, msg_stride, d_msg_len, d_out, n, DEVICE)
 
 
 def expand_message_xmd(ctx: "Context", hash_id: int, msgs: Sequence[bytes], dst: bytes, out_bytes: int) -> np.ndarray:
     """ExpandMsgXmd::expand_message for a batch on the device -> (n, out_bytes) uniform bytes (ecgpu_expand_message_xmd_batch)"""
-    rec, lens, stride = pack_messages(msgs)
+    m = _host_messages(msgs, aligned=False)
     out = _host_out(len(msgs), out_bytes)
-    d = np.frombuffer(bytes(dst), dtype=np.uint8)
-    ctx.check(ctx.lib.ecgpu_expand_message_xmd_batch(ctx.handle, hash_id, _ptr(rec)[0] if stride else None, stride, _ptr(lens)[0], _ptr(d)[0] if len(d) else None,
-                                                     len(d), _ptr(out)[0], out_bytes, len(msgs), HOST))
+    _call(ctx, "ecgpu_expand_message_xmd_batch", hash_id, *m, *_host_dst(dst), out, out_bytes, len(msgs), HOST)
     return out
 
 
@@ -400,13 +405,18 @@ class Curve:
     def __init__(self, ctx: Context, cid: int):
         self.ctx, self.id, self.nb = ctx, cid, FIELD_BYTES[cid]
 
+    def _call(self, name: str, *args):
+        _call(self.ctx, name, self.id, *args)
+
+    def _flags(self, flags: Optional[int]) -> int:
+        return self.default_ecdsa_flags() if flags is None else flags
+
     # --- FieldElement -----------------------------------------------------------------------
     def field_op(self, op: int, a, b=None) -> np.ndarray:
         a = _as_host(a, self.nb)
         bb = _as_host(b, self.nb) if b is not None else None
         out = _host_out(len(a), self.nb)
-        pa, _ = _ptr(a); pb, _ = _ptr(bb); po, _ = _ptr(out)
-        self.ctx.check(self.ctx.lib.ecgpu_field_op_batch(self.ctx.handle, self.id, op, pa, pb, po, len(a), HOST))
+        self._call("ecgpu_field_op_batch", op, a, bb, out, len(a), HOST)
         return out
 
     # --- Scalar ------------------------------------------------------------------------------
@@ -419,9 +429,8 @@ class Curve:
         bb = _as_host(b, self.nb) if b is not None and op in SC_BINARY else None
         if bb is not None and len(bb) != len(a):
             raise ValueError("a and b differ in length (%d, %d)" % (len(a), len(bb)))
-        out, ok = _host_out(len(a), self.nb), np.zeros(len(a), dtype=np.uint8)
-        pa, _ = _ptr(a); pb, _ = _ptr(bb); po, _ = _ptr(out); pk, _ = _ptr(ok)
-        self.ctx.check(self.ctx.lib.ecgpu_scalar_op_batch(self.ctx.handle, self.id, op, pa, pb, po, pk, len(a), HOST))
+        out, ok = _host_out(len(a), self.nb), _host_flags(len(a))
+        self._call("ecgpu_scalar_op_batch", op, a, bb, out, ok, len(a), HOST)
         return out, ok
 
     def scalar_op_device(self, op: int, d_a, d_b, d_out, d_ok, n: int):
@@ -433,8 +442,7 @@ class Curve:
             self._check_device(d_b, n * self.nb, "d_b")
         self._check_device(d_out, n * self.nb, "d_out")
         self._check_device(d_ok, n, "d_ok")
-        self.ctx.check(self.ctx.lib.ecgpu_scalar_op_batch(self.ctx.handle, self.id, op, _ptr(d_a)[0], _ptr(d_b if op in SC_BINARY else None)[0],
-                                                          _ptr(d_out)[0], _ptr(d_ok)[0], n, DEVICE))
+        self._call("ecgpu_scalar_op_batch", op, d_a, d_b if op in SC_BINARY else None, d_out, d_ok, n, DEVICE)
 
     def scalar_reduce(self, data, nonzero: bool = False, in_bytes: Optional[int] = None) -> np.ndarray:
         """Reduce / ReduceNonZero / FromOkm: big-endian records of in_bytes bytes (1 .. 2 NB; default: the width of a 2-D
@@ -445,54 +453,52 @@ class Curve:
             in_bytes = data.shape[1]
         d = _as_host(data, in_bytes)
         out = _host_out(len(d), self.nb)
-        self.ctx.check(self.ctx.lib.ecgpu_scalar_reduce_batch(self.ctx.handle, self.id, _ptr(d)[0], in_bytes, _ptr(out)[0], len(d), HOST,
-                                                              REDUCE_NONZERO if nonzero else 0))
+        self._call("ecgpu_scalar_reduce_batch", d, in_bytes, out, len(d), HOST, REDUCE_NONZERO if nonzero else 0)
         return out
 
     # --- ProjectivePoint::{add, add_mixed, double}, BatchNormalize ------------------------------
     def add(self, p_xyz, q_xyz) -> np.ndarray:
         p, q = _as_host(p_xyz, 3 * self.nb), _as_host(q_xyz, 3 * self.nb)
         out = _host_out(len(p), 3 * self.nb)
-        self.ctx.check(self.ctx.lib.ecgpu_point_add_batch(self.ctx.handle, self.id, _ptr(p)[0], _ptr(q)[0], _ptr(out)[0], len(p), HOST))
+        self._call("ecgpu_point_add_batch", p, q, out, len(p), HOST)
         return out
 
     def add_mixed(self, p_xyz, q_xy) -> np.ndarray:
         p, q = _as_host(p_xyz, 3 * self.nb), _as_host(q_xy, 2 * self.nb)
         out = _host_out(len(p), 3 * self.nb)
-        self.ctx.check(self.ctx.lib.ecgpu_point_add_mixed_batch(self.ctx.handle, self.id, _ptr(p)[0], _ptr(q)[0], _ptr(out)[0], len(p), HOST))
+        self._call("ecgpu_point_add_mixed_batch", p, q, out, len(p), HOST)
         return out
 
     def double(self, p_xyz) -> np.ndarray:
         p = _as_host(p_xyz, 3 * self.nb)
         out = _host_out(len(p), 3 * self.nb)
-        self.ctx.check(self.ctx.lib.ecgpu_point_double_batch(self.ctx.handle, self.id, _ptr(p)[0], _ptr(out)[0], len(p), HOST))
+        self._call("ecgpu_point_double_batch", p, out, len(p), HOST)
         return out
 
     def batch_normalize(self, p_xyz):
         p = _as_host(p_xyz, 3 * self.nb)
-        out, inf = _host_out(len(p), 2 * self.nb), np.zeros(len(p), dtype=np.uint8)
-        self.ctx.check(self.ctx.lib.ecgpu_batch_normalize(self.ctx.handle, self.id, _ptr(p)[0], _ptr(out)[0], _ptr(inf)[0], len(p), HOST))
+        out, inf = _host_out(len(p), 2 * self.nb), _host_flags(len(p))
+        self._call("ecgpu_batch_normalize", p, out, inf, len(p), HOST)
         return out, inf
 
     def add_device(self, d_p_xyz, d_q_xyz, d_out_xyz, n: int):
         """complete addition on device-resident projective points (torch tensors / device pointers)"""
         for t, nm in ((d_p_xyz, "d_p_xyz"), (d_q_xyz, "d_q_xyz"), (d_out_xyz, "d_out_xyz")):
             self._check_device(t, n * 3 * self.nb, nm)
-        self.ctx.check(self.ctx.lib.ecgpu_point_add_batch(self.ctx.handle, self.id, _ptr(d_p_xyz)[0], _ptr(d_q_xyz)[0], _ptr(d_out_xyz)[0], n, DEVICE))
+        self._call("ecgpu_point_add_batch", d_p_xyz, d_q_xyz, d_out_xyz, n, DEVICE)
 
     def batch_normalize_device(self, d_p_xyz, d_out_xy, d_out_inf, n: int):
         self._check_device(d_p_xyz, n * 3 * self.nb, "d_p_xyz")
         self._check_device(d_out_xy, n * 2 * self.nb, "d_out_xy")
         self._check_device(d_out_inf, n, "d_out_inf")
-        self.ctx.check(self.ctx.lib.ecgpu_batch_normalize(self.ctx.handle, self.id, _ptr(d_p_xyz)[0], _ptr(d_out_xy)[0], _ptr(d_out_inf)[0], n, DEVICE))
+        self._call("ecgpu_batch_normalize", d_p_xyz, d_out_xy, d_out_inf, n, DEVICE)
 
     def point_eq(self, p_xyz, q_xyz) -> np.ndarray:
         """ProjectivePoint == ProjectivePoint (ct_eq) per element -> uint8 flags"""
         p, q = _as_host(p_xyz, 3 * self.nb), _as_host(q_xyz, 3 * self.nb)
-        if len(p) != len(q):
-            raise ValueError("point batches differ in length")
-        eq = np.zeros(len(p), dtype=np.uint8)
-        self.ctx.check(self.ctx.lib.ecgpu_point_eq_batch(self.ctx.handle, self.id, _ptr(p)[0], _ptr(q)[0], _ptr(eq)[0], len(p), HOST))
+        _equal_lengths("point", p, q)
+        eq = _host_flags(len(p))
+        self._call("ecgpu_point_eq_batch", p, q, eq, len(p), HOST)
         return eq
 
     # --- Mul<Scalar>, MulByGenerator, LinearCombination -----------------------------------------
@@ -504,23 +510,20 @@ class Curve:
         if terms < 1 or len(s) % terms:
             raise ValueError("the number of scalars is not a multiple of `terms`")
         n = len(s) // terms
-        pw = (3 if point_format == PROJECTIVE else 2) * self.nb
-        ow = (3 if out_format == PROJECTIVE else 2) * self.nb
-        p = _as_host(points, pw) if points is not None else None
+        ow = _point_bytes(out_format, self.nb)
+        p = _as_host(points, _point_bytes(point_format, self.nb)) if points is not None else None
         if p is not None and len(p) != n * terms:
             raise ValueError("scalars and points differ in count (%d scalars, %d points)" % (len(s), len(p)))
         out = _host_out(n, ow) if out is None else out
-        inf = np.zeros(n, dtype=np.uint8) if out_inf is None else out_inf
+        inf = _host_flags(n) if out_inf is None else out_inf
         if (out.shape != (n, ow) or out.dtype != np.uint8 or not out.flags.c_contiguous
                 or inf.shape != (n,) or inf.dtype != np.uint8 or not inf.flags.c_contiguous):
             raise ValueError("out / out_inf have the wrong shape, dtype or layout")
         if checked:
-            ok = np.zeros(n, dtype=np.uint8)
-            self.ctx.check(self.ctx.lib.ecgpu_lincomb_batch_checked(self.ctx.handle, self.id, _ptr(s)[0], _ptr(p)[0], point_format, terms,
-                                                                    _ptr(out)[0], out_format, _ptr(inf)[0], _ptr(ok)[0], n, HOST, flags))
+            ok = _host_flags(n)
+            self._call("ecgpu_lincomb_batch_checked", s, p, point_format, terms, out, out_format, inf, ok, n, HOST, flags)
             return (out, inf, ok) if out_format == AFFINE else (out, ok)
-        self.ctx.check(self.ctx.lib.ecgpu_lincomb_batch(self.ctx.handle, self.id, _ptr(s)[0], _ptr(p)[0], point_format, terms,
-                                                        _ptr(out)[0], out_format, _ptr(inf)[0], n, HOST, flags))
+        self._call("ecgpu_lincomb_batch", s, p, point_format, terms, out, out_format, inf, n, HOST, flags)
         return (out, inf) if out_format == AFFINE else out
 
     def mul(self, scalars, points, point_format: int = AFFINE, out_format: int = AFFINE, flags: int = 0, out=None, out_inf=None):
@@ -542,10 +545,9 @@ class Curve:
     def ecdh(self, secret_scalars, public_keys_xy):
         """ecgpu_ecdh_batch -> (shared_x (n, NB), ok (n,)): ok = 0 and zeros for a zero / out-of-range secret or an invalid key"""
         d, q = _as_host(secret_scalars, self.nb), _as_host(public_keys_xy, 2 * self.nb)
-        if len(d) != len(q):
-            raise ValueError("secret and public-key batches differ in length")
-        out, ok = _host_out(len(d), self.nb), np.zeros(len(d), dtype=np.uint8)
-        self.ctx.check(self.ctx.lib.ecgpu_ecdh_batch(self.ctx.handle, self.id, _ptr(d)[0], _ptr(q)[0], _ptr(out)[0], _ptr(ok)[0], len(d), HOST))
+        _equal_lengths("secret and public-key", d, q)
+        out, ok = _host_out(len(d), self.nb), _host_flags(len(d))
+        self._call("ecgpu_ecdh_batch", d, q, out, ok, len(d), HOST)
         return out, ok
 
     def ecdh_device(self, d_secret, d_pubkeys_xy, d_shared_x, d_ok, n: int):
@@ -553,7 +555,7 @@ class Curve:
         self._check_device(d_pubkeys_xy, n * 2 * self.nb, "d_pubkeys_xy")
         self._check_device(d_shared_x, n * self.nb, "d_shared_x")
         self._check_device(d_ok, n, "d_ok")
-        self.ctx.check(self.ctx.lib.ecgpu_ecdh_batch(self.ctx.handle, self.id, _ptr(d_secret)[0], _ptr(d_pubkeys_xy)[0], _ptr(d_shared_x)[0], _ptr(d_ok)[0], n, DEVICE))
+        self._call("ecgpu_ecdh_batch", d_secret, d_pubkeys_xy, d_shared_x, d_ok, n, DEVICE)
 
     def _check_device(self, t, need_bytes: int, what: str):
         """size check for torch tensors handed to the *_device methods (raw integer pointers cannot be checked)"""
@@ -563,74 +565,71 @@ class Curve:
     def mul_device(self, d_scalars, d_points, d_out, n: int, point_format: int = AFFINE, out_format: int = AFFINE,
                    d_out_inf=None, flags: int = 0):
         self._check_device(d_scalars, n * self.nb, "d_scalars")
-        self._check_device(d_points, n * (3 if point_format == PROJECTIVE else 2) * self.nb, "d_points")
-        self._check_device(d_out, n * (3 if out_format == PROJECTIVE else 2) * self.nb, "d_out")
+        self._check_device(d_points, n * _point_bytes(point_format, self.nb), "d_points")
+        self._check_device(d_out, n * _point_bytes(out_format, self.nb), "d_out")
         self._check_device(d_out_inf, n, "d_out_inf")
-        self.ctx.check(self.ctx.lib.ecgpu_mul_batch(self.ctx.handle, self.id, _ptr(d_scalars)[0], _ptr(d_points)[0], point_format,
-                                                    _ptr(d_out)[0], out_format, _ptr(d_out_inf)[0], n, DEVICE, flags))
+        self._call("ecgpu_mul_batch", d_scalars, d_points, point_format, d_out, out_format, d_out_inf, n, DEVICE, flags)
 
     def msm(self, scalars, points, point_format: int = AFFINE, out_format: int = AFFINE) -> np.ndarray:
         s = _as_host(scalars, self.nb)
-        pw = (3 if point_format == PROJECTIVE else 2) * self.nb
-        p = _as_host(points, pw)
+        p = _as_host(points, _point_bytes(point_format, self.nb))
         if len(p) != len(s):
             raise ValueError("scalars and points differ in count (%d scalars, %d points)" % (len(s), len(p)))
-        out = _host_out(1, (3 if out_format == PROJECTIVE else 2) * self.nb)
-        self.ctx.check(self.ctx.lib.ecgpu_msm(self.ctx.handle, self.id, _ptr(s)[0], _ptr(p)[0], point_format, len(s), _ptr(out)[0], out_format, HOST))
+        out = _host_out(1, _point_bytes(out_format, self.nb))
+        self._call("ecgpu_msm", s, p, point_format, len(s), out, out_format, HOST)
         return out[0]
 
     def msm_device(self, d_scalars, d_points, n: int, d_out, point_format: int = AFFINE, out_format: int = AFFINE):
         self._check_device(d_scalars, n * self.nb, "d_scalars")
-        self._check_device(d_points, n * (3 if point_format == PROJECTIVE else 2) * self.nb, "d_points")
-        self._check_device(d_out, (3 if out_format == PROJECTIVE else 2) * self.nb, "d_out")
-        self.ctx.check(self.ctx.lib.ecgpu_msm(self.ctx.handle, self.id, _ptr(d_scalars)[0], _ptr(d_points)[0], point_format, n,
-                                              _ptr(d_out)[0], out_format, DEVICE))
+        self._check_device(d_points, n * _point_bytes(point_format, self.nb), "d_points")
+        self._check_device(d_out, _point_bytes(out_format, self.nb), "d_out")
+        self._call("ecgpu_msm", d_scalars, d_points, point_format, n, d_out, out_format, DEVICE)
 
     # --- decoding ---------------------------------------------------------------------------------
     def validate_scalars(self, scalars) -> np.ndarray:
         s = _as_host(scalars, self.nb)
-        ok = np.zeros(len(s), dtype=np.uint8)
-        self.ctx.check(self.ctx.lib.ecgpu_validate_scalars(self.ctx.handle, self.id, _ptr(s)[0], _ptr(ok)[0], len(s), HOST))
+        ok = _host_flags(len(s))
+        self._call("ecgpu_validate_scalars", s, ok, len(s), HOST)
         return ok
 
     def validate_points(self, points_xy) -> np.ndarray:
         p = _as_host(points_xy, 2 * self.nb)
-        ok = np.zeros(len(p), dtype=np.uint8)
-        self.ctx.check(self.ctx.lib.ecgpu_validate_points(self.ctx.handle, self.id, _ptr(p)[0], _ptr(ok)[0], len(p), HOST))
+        ok = _host_flags(len(p))
+        self._call("ecgpu_validate_points", p, ok, len(p), HOST)
         return ok
 
     def decompress(self, xs, y_is_odd):
         x = _as_host(xs, self.nb)
         odd = np.ascontiguousarray(y_is_odd, dtype=np.uint8)
-        out, ok = _host_out(len(x), 2 * self.nb), np.zeros(len(x), dtype=np.uint8)
-        self.ctx.check(self.ctx.lib.ecgpu_decompress_batch(self.ctx.handle, self.id, _ptr(x)[0], _ptr(odd)[0], _ptr(out)[0], _ptr(ok)[0], len(x), HOST))
+        out, ok = _host_out(len(x), 2 * self.nb), _host_flags(len(x))
+        self._call("ecgpu_decompress_batch", x, odd, out, ok, len(x), HOST)
         return out, ok
 
     # --- GroupEncoding::{to_bytes, from_bytes} ------------------------------------------------------
     def to_bytes(self, points, point_format: int = AFFINE) -> np.ndarray:
-        p = _as_host(points, (3 if point_format == PROJECTIVE else 2) * self.nb)
+        p = _as_host(points, _point_bytes(point_format, self.nb))
         out = _host_out(len(p), self.nb + 1)
-        self.ctx.check(self.ctx.lib.ecgpu_to_bytes_batch(self.ctx.handle, self.id, _ptr(p)[0], point_format, _ptr(out)[0], len(p), HOST))
+        self._call("ecgpu_to_bytes_batch", p, point_format, out, len(p), HOST)
         return out
 
     def from_bytes(self, encoded):
         e = _as_host(encoded, self.nb + 1)
-        out, ok = _host_out(len(e), 2 * self.nb), np.zeros(len(e), dtype=np.uint8)
-        self.ctx.check(self.ctx.lib.ecgpu_from_bytes_batch(self.ctx.handle, self.id, _ptr(e)[0], _ptr(out)[0], _ptr(ok)[0], len(e), HOST))
+        out, ok = _host_out(len(e), 2 * self.nb), _host_flags(len(e))
+        self._call("ecgpu_from_bytes_batch", e, out, ok, len(e), HOST)
         return out, ok
 
     # --- ToEncodedPoint::to_encoded_point / FromEncodedPoint::from_encoded_point (fixed-width records) -------------
     def sec1_encode(self, points, compress: bool = False, point_format: int = AFFINE) -> np.ndarray:
-        p = _as_host(points, (3 if point_format == PROJECTIVE else 2) * self.nb)
+        p = _as_host(points, _point_bytes(point_format, self.nb))
         out = _host_out(len(p), 1 + (1 if compress else 2) * self.nb)
-        self.ctx.check(self.ctx.lib.ecgpu_sec1_encode_batch(self.ctx.handle, self.id, _ptr(p)[0], point_format, int(bool(compress)), _ptr(out)[0], len(p), HOST))
+        self._call("ecgpu_sec1_encode_batch", p, point_format, int(bool(compress)), out, len(p), HOST)
         return out
 
     def sec1_decode(self, encoded, record_bytes: Optional[int] = None):
         rb = record_bytes or (1 + 2 * self.nb)
         e = _as_host(encoded, rb)
-        out, ok = _host_out(len(e), 2 * self.nb), np.zeros(len(e), dtype=np.uint8)
-        self.ctx.check(self.ctx.lib.ecgpu_sec1_decode_batch(self.ctx.handle, self.id, _ptr(e)[0], rb, _ptr(out)[0], _ptr(ok)[0], len(e), HOST))
+        out, ok = _host_out(len(e), 2 * self.nb), _host_flags(len(e))
+        self._call("ecgpu_sec1_decode_batch", e, rb, out, ok, len(e), HOST)
         return out, ok
 
     # --- ECDSA: VerifyPrimitive::verify_prehashed / SignPrimitive::try_sign_prehashed ------------------
@@ -640,51 +639,43 @@ class Curve:
 
     def ecdsa_verify(self, prehash, sig_rs, pubkeys_xy, flags: Optional[int] = None) -> np.ndarray:
         z, sg, q = _as_host(prehash, self.nb), _as_host(sig_rs, 2 * self.nb), _as_host(pubkeys_xy, 2 * self.nb)
-        if not (len(z) == len(sg) == len(q)):
-            raise ValueError("prehash, signature and public-key batches differ in length")
-        ok = np.zeros(len(z), dtype=np.uint8)
-        fl = self.default_ecdsa_flags() if flags is None else flags
-        self.ctx.check(self.ctx.lib.ecgpu_ecdsa_verify_batch(self.ctx.handle, self.id, _ptr(z)[0], _ptr(sg)[0], _ptr(q)[0], _ptr(ok)[0], len(z), HOST, fl))
+        _equal_lengths("prehash, signature and public-key", z, sg, q)
+        ok = _host_flags(len(z))
+        self._call("ecgpu_ecdsa_verify_batch", z, sg, q, ok, len(z), HOST, self._flags(flags))
         return ok
 
     def ecdsa_verify_device(self, d_prehash, d_sig_rs, d_pubkeys_xy, d_ok, n: int, flags: Optional[int] = None):
-        fl = self.default_ecdsa_flags() if flags is None else flags
-        self.ctx.check(self.ctx.lib.ecgpu_ecdsa_verify_batch(self.ctx.handle, self.id, _ptr(d_prehash)[0], _ptr(d_sig_rs)[0], _ptr(d_pubkeys_xy)[0],
-                                                             _ptr(d_ok)[0], n, DEVICE, fl))
+        self._call("ecgpu_ecdsa_verify_batch", d_prehash, d_sig_rs, d_pubkeys_xy, d_ok, n, DEVICE, self._flags(flags))
 
     def map_to_curve(self, u, count: int = 1):
         """MapToCurve::map_to_curve (count = 1) or Q0 + Q1 of hash_from_bytes (count = 2) -> (points_xy, inf)"""
         uu = _as_host(u, self.nb)
         n = len(uu) // count
-        out, inf = _host_out(n, 2 * self.nb), np.zeros(n, dtype=np.uint8)
-        self.ctx.check(self.ctx.lib.ecgpu_map_to_curve_batch(self.ctx.handle, self.id, _ptr(uu)[0], count, _ptr(out)[0], _ptr(inf)[0], n, HOST))
+        out, inf = _host_out(n, 2 * self.nb), _host_flags(n)
+        self._call("ecgpu_map_to_curve_batch", uu, count, out, inf, n, HOST)
         return out, inf
 
     # --- GroupDigest / FromOkm: everything that starts from bytes (SHA-2, expand_message_xmd and the reductions run on the device)
     def hash_to_curve(self, msgs: Sequence[bytes], dst: bytes, mode: int = H2C_RO):
         """GroupDigest::hash_from_bytes (H2C_RO) / encode_from_bytes (H2C_NU), one message per element -> (points_xy, inf)"""
-        rec, lens, stride = pack_messages(msgs)
+        m = _host_messages(msgs, aligned=False)
         n = len(msgs)
-        out, inf = _host_out(n, 2 * self.nb), np.zeros(n, dtype=np.uint8)
-        d = np.frombuffer(bytes(dst), dtype=np.uint8)
-        self.ctx.check(self.ctx.lib.ecgpu_hash_to_curve_batch(self.ctx.handle, self.id, _ptr(rec)[0] if stride else None, stride, _ptr(lens)[0],
-                                                              _ptr(d)[0] if len(d) else None, len(d), mode, _ptr(out)[0], _ptr(inf)[0], n, HOST))
+        out, inf = _host_out(n, 2 * self.nb), _host_flags(n)
+        self._call("ecgpu_hash_to_curve_batch", *m, *_host_dst(dst), mode, out, inf, n, HOST)
         return out, inf
 
     def hash_to_scalar(self, msgs: Sequence[bytes], dst: bytes) -> np.ndarray:
         """GroupDigest::hash_to_scalar -> (n, NB) canonical scalars"""
-        rec, lens, stride = pack_messages(msgs)
+        m = _host_messages(msgs, aligned=False)
         out = _host_out(len(msgs), self.nb)
-        d = np.frombuffer(bytes(dst), dtype=np.uint8)
-        self.ctx.check(self.ctx.lib.ecgpu_hash_to_scalar_batch(self.ctx.handle, self.id, _ptr(rec)[0] if stride else None, stride, _ptr(lens)[0],
-                                                               _ptr(d)[0] if len(d) else None, len(d), _ptr(out)[0], len(msgs), HOST))
+        self._call("ecgpu_hash_to_scalar_batch", *m, *_host_dst(dst), out, len(msgs), HOST)
         return out
 
     def field_from_okm(self, okm) -> np.ndarray:
         """FromOkm for FieldElement: big-endian records of L bytes (48, p384: 72) -> canonical field elements okm mod p"""
         o = _as_host(okm, OKM_BYTES[self.id])
         out = _host_out(len(o), self.nb)
-        self.ctx.check(self.ctx.lib.ecgpu_field_from_okm_batch(self.ctx.handle, self.id, _ptr(o)[0], _ptr(out)[0], len(o), HOST))
+        self._call("ecgpu_field_from_okm_batch", o, out, len(o), HOST)
         return out
 
     def expand_message_xmd(self, msgs: Sequence[bytes], dst: bytes, out_bytes: int) -> np.ndarray:
@@ -694,57 +685,44 @@ class Curve:
     def schnorr_verify_prehash(self, pubkeys_x, sig_rs, prehashes) -> np.ndarray:
         """VerifyingKey::verify_prehash for a batch: the BIP340 challenge hashes are computed on the device as well"""
         x, sg, m = _as_host(pubkeys_x, self.nb), _as_host(sig_rs, 2 * self.nb), _as_host(prehashes, 32)
-        if not (len(x) == len(sg) == len(m)):
-            raise ValueError("key, signature and prehash batches differ in length")
-        ok = np.zeros(len(x), dtype=np.uint8)
-        self.ctx.check(self.ctx.lib.ecgpu_schnorr_verify_prehash_batch(self.ctx.handle, self.id, _ptr(x)[0], _ptr(sg)[0], _ptr(m)[0], _ptr(ok)[0], len(x), HOST))
+        _equal_lengths("key, signature and prehash", x, sg, m)
+        ok = _host_flags(len(x))
+        self._call("ecgpu_schnorr_verify_prehash_batch", x, sg, m, ok, len(x), HOST)
         return ok
 
     def ecdsa_recover(self, prehash, sig_rs, recovery_id, flags: Optional[int] = None):
         """VerifyingKey::recover_from_prehash for a batch -> (pubkeys_xy, ok)"""
         z, sg = _as_host(prehash, self.nb), _as_host(sig_rs, 2 * self.nb)
         rid = np.ascontiguousarray(recovery_id, dtype=np.uint8).reshape(-1)
-        if not (len(z) == len(sg) == len(rid)):
-            raise ValueError("prehash, signature and recovery-id batches differ in length")
-        out, ok = _host_out(len(z), 2 * self.nb), np.zeros(len(z), dtype=np.uint8)
-        fl = self.default_ecdsa_flags() if flags is None else flags
-        self.ctx.check(self.ctx.lib.ecgpu_ecdsa_recover_batch(self.ctx.handle, self.id, _ptr(z)[0], _ptr(sg)[0], _ptr(rid)[0], _ptr(out)[0], _ptr(ok)[0],
-                                                              len(z), HOST, fl))
+        _equal_lengths("prehash, signature and recovery-id", z, sg, rid)
+        out, ok = _host_out(len(z), 2 * self.nb), _host_flags(len(z))
+        self._call("ecgpu_ecdsa_recover_batch", z, sg, rid, out, ok, len(z), HOST, self._flags(flags))
         return out, ok
 
     def ecdsa_recover_device(self, d_prehash, d_sig_rs, d_recid, d_pubkeys_xy, d_ok, n: int, flags: Optional[int] = None):
-        fl = self.default_ecdsa_flags() if flags is None else flags
-        self.ctx.check(self.ctx.lib.ecgpu_ecdsa_recover_batch(self.ctx.handle, self.id, _ptr(d_prehash)[0], _ptr(d_sig_rs)[0], _ptr(d_recid)[0],
-                                                              _ptr(d_pubkeys_xy)[0], _ptr(d_ok)[0], n, DEVICE, fl))
+        self._call("ecgpu_ecdsa_recover_batch", d_prehash, d_sig_rs, d_recid, d_pubkeys_xy, d_ok, n, DEVICE, self._flags(flags))
 
     def schnorr_verify(self, pubkeys_x, sig_rs, challenges) -> np.ndarray:
         """EC part of BIP340 verification; challenges = tagged challenge hashes (ecgpu.schnorr computes them)."""
         x, sg, e = _as_host(pubkeys_x, self.nb), _as_host(sig_rs, 2 * self.nb), _as_host(challenges, self.nb)
-        if not (len(x) == len(sg) == len(e)):
-            raise ValueError("key, signature and challenge batches differ in length")
-        ok = np.zeros(len(x), dtype=np.uint8)
-        self.ctx.check(self.ctx.lib.ecgpu_schnorr_verify_batch(self.ctx.handle, self.id, _ptr(x)[0], _ptr(sg)[0], _ptr(e)[0], _ptr(ok)[0], len(x), HOST))
+        _equal_lengths("key, signature and challenge", x, sg, e)
+        ok = _host_flags(len(x))
+        self._call("ecgpu_schnorr_verify_batch", x, sg, e, ok, len(x), HOST)
         return ok
 
     def schnorr_verify_device(self, d_pubkeys_x, d_sig_rs, d_challenges, d_ok, n: int):
-        self.ctx.check(self.ctx.lib.ecgpu_schnorr_verify_batch(self.ctx.handle, self.id, _ptr(d_pubkeys_x)[0], _ptr(d_sig_rs)[0], _ptr(d_challenges)[0],
-                                                               _ptr(d_ok)[0], n, DEVICE))
+        self._call("ecgpu_schnorr_verify_batch", d_pubkeys_x, d_sig_rs, d_challenges, d_ok, n, DEVICE)
 
     def ecdsa_sign(self, secret_d, nonce_k, prehash, flags: Optional[int] = None):
         """-> (sig_rs, recovery_id, ok)"""
         d, k, z = _as_host(secret_d, self.nb), _as_host(nonce_k, self.nb), _as_host(prehash, self.nb)
-        if not (len(d) == len(k) == len(z)):
-            raise ValueError("key, nonce and prehash batches differ in length")
-        sig, rec, ok = _host_out(len(d), 2 * self.nb), np.zeros(len(d), dtype=np.uint8), np.zeros(len(d), dtype=np.uint8)
-        fl = self.default_ecdsa_flags() if flags is None else flags
-        self.ctx.check(self.ctx.lib.ecgpu_ecdsa_sign_batch(self.ctx.handle, self.id, _ptr(d)[0], _ptr(k)[0], _ptr(z)[0], _ptr(sig)[0], _ptr(rec)[0],
-                                                           _ptr(ok)[0], len(d), HOST, fl))
+        _equal_lengths("key, nonce and prehash", d, k, z)
+        sig, rec, ok = _host_out(len(d), 2 * self.nb), _host_flags(len(d)), _host_flags(len(d))
+        self._call("ecgpu_ecdsa_sign_batch", d, k, z, sig, rec, ok, len(d), HOST, self._flags(flags))
         return sig, rec, ok
 
     def ecdsa_sign_device(self, d_secret, d_nonce, d_prehash, d_sig_rs, d_recid, d_ok, n: int, flags: Optional[int] = None):
-        fl = self.default_ecdsa_flags() if flags is None else flags
-        self.ctx.check(self.ctx.lib.ecgpu_ecdsa_sign_batch(self.ctx.handle, self.id, _ptr(d_secret)[0], _ptr(d_nonce)[0], _ptr(d_prehash)[0],
-                                                           _ptr(d_sig_rs)[0], _ptr(d_recid)[0], _ptr(d_ok)[0], n, DEVICE, fl))
+        self._call("ecgpu_ecdsa_sign_batch", d_secret, d_nonce, d_prehash, d_sig_rs, d_recid, d_ok, n, DEVICE, self._flags(flags))
 
     # --- deterministic signing: the nonce is derived on the device (RFC 6979 / BIP340) -------------------
     def rfc6979_nonce(self, secret_d, prehash, extra=None) -> np.ndarray:
@@ -752,46 +730,36 @@ class Curve:
         randomized forms, field-sized) -> (n, NB); zeros for a key outside [1, n-1]"""
         d, z = _as_host(secret_d, self.nb), _as_host(prehash, self.nb)
         x = None if extra is None else _as_host(extra, self.nb)
-        if len(d) != len(z) or (x is not None and len(x) != len(d)):
-            raise ValueError("key, prehash and additional-data batches differ in length")
+        _equal_lengths("key, prehash and additional-data", d, z, x)
         k = _host_out(len(d), self.nb)
-        self.ctx.check(self.ctx.lib.ecgpu_rfc6979_nonce_batch(self.ctx.handle, self.id, _ptr(d)[0], _ptr(z)[0], _ptr(x)[0], _ptr(k)[0], len(d), HOST))
+        self._call("ecgpu_rfc6979_nonce_batch", d, z, x, k, len(d), HOST)
         return k
 
     def rfc6979_nonce_device(self, d_secret, d_prehash, d_extra, d_out_k, n: int):
-        self.ctx.check(self.ctx.lib.ecgpu_rfc6979_nonce_batch(self.ctx.handle, self.id, _ptr(d_secret)[0], _ptr(d_prehash)[0], _ptr(d_extra)[0],
-                                                              _ptr(d_out_k)[0], n, DEVICE))
+        self._call("ecgpu_rfc6979_nonce_batch", d_secret, d_prehash, d_extra, d_out_k, n, DEVICE)
 
     def ecdsa_sign_prehash(self, secret_d, prehash, extra=None, flags: Optional[int] = None):
         """PrehashSigner::sign_prehash (extra=None) / RandomizedPrehashSigner (extra given) for a batch -> (sig_rs, recovery_id, ok)"""
         d, z = _as_host(secret_d, self.nb), _as_host(prehash, self.nb)
         x = None if extra is None else _as_host(extra, self.nb)
-        if len(d) != len(z) or (x is not None and len(x) != len(d)):
-            raise ValueError("key, prehash and additional-data batches differ in length")
-        sig, rec, ok = _host_out(len(d), 2 * self.nb), np.zeros(len(d), dtype=np.uint8), np.zeros(len(d), dtype=np.uint8)
-        fl = self.default_ecdsa_flags() if flags is None else flags
-        self.ctx.check(self.ctx.lib.ecgpu_ecdsa_sign_prehash_batch(self.ctx.handle, self.id, _ptr(d)[0], _ptr(z)[0], _ptr(x)[0], _ptr(sig)[0], _ptr(rec)[0],
-                                                                   _ptr(ok)[0], len(d), HOST, fl))
+        _equal_lengths("key, prehash and additional-data", d, z, x)
+        sig, rec, ok = _host_out(len(d), 2 * self.nb), _host_flags(len(d)), _host_flags(len(d))
+        self._call("ecgpu_ecdsa_sign_prehash_batch", d, z, x, sig, rec, ok, len(d), HOST, self._flags(flags))
         return sig, rec, ok
 
     def ecdsa_sign_prehash_device(self, d_secret, d_prehash, d_extra, d_sig_rs, d_recid, d_ok, n: int, flags: Optional[int] = None):
-        fl = self.default_ecdsa_flags() if flags is None else flags
-        self.ctx.check(self.ctx.lib.ecgpu_ecdsa_sign_prehash_batch(self.ctx.handle, self.id, _ptr(d_secret)[0], _ptr(d_prehash)[0], _ptr(d_extra)[0],
-                                                                   _ptr(d_sig_rs)[0], _ptr(d_recid)[0], _ptr(d_ok)[0], n, DEVICE, fl))
+        self._call("ecgpu_ecdsa_sign_prehash_batch", d_secret, d_prehash, d_extra, d_sig_rs, d_recid, d_ok, n, DEVICE, self._flags(flags))
 
     def schnorr_sign_prehash(self, secret_keys, prehashes, aux_rands):
         """BIP340 SigningKey::sign_prehash_with_aux_rand for a batch (secp256k1) -> (sig_rs, pubkeys_x, ok)"""
         d, m, a = _as_host(secret_keys, self.nb), _as_host(prehashes, 32), _as_host(aux_rands, 32)
-        if not (len(d) == len(m) == len(a)):
-            raise ValueError("key, prehash and aux_rand batches differ in length")
-        sig, px, ok = _host_out(len(d), 2 * self.nb), _host_out(len(d), self.nb), np.zeros(len(d), dtype=np.uint8)
-        self.ctx.check(self.ctx.lib.ecgpu_schnorr_sign_prehash_batch(self.ctx.handle, self.id, _ptr(d)[0], _ptr(m)[0], _ptr(a)[0], _ptr(sig)[0], _ptr(px)[0],
-                                                                     _ptr(ok)[0], len(d), HOST))
+        _equal_lengths("key, prehash and aux_rand", d, m, a)
+        sig, px, ok = _host_out(len(d), 2 * self.nb), _host_out(len(d), self.nb), _host_flags(len(d))
+        self._call("ecgpu_schnorr_sign_prehash_batch", d, m, a, sig, px, ok, len(d), HOST)
         return sig, px, ok
 
     def schnorr_sign_prehash_device(self, d_secret, d_prehash, d_aux, d_sig_rs, d_pubkeys_x, d_ok, n: int):
-        self.ctx.check(self.ctx.lib.ecgpu_schnorr_sign_prehash_batch(self.ctx.handle, self.id, _ptr(d_secret)[0], _ptr(d_prehash)[0], _ptr(d_aux)[0],
-                                                                     _ptr(d_sig_rs)[0], _ptr(d_pubkeys_x)[0], _ptr(d_ok)[0], n, DEVICE))
+        self._call("ecgpu_schnorr_sign_prehash_batch", d_secret, d_prehash, d_aux, d_sig_rs, d_pubkeys_x, d_ok, n, DEVICE)
 
     # --- from message bytes: the curve's own digest runs on the device, then the prehash pipeline -------------
     def digest(self, msgs: Sequence[bytes]) -> np.ndarray:
@@ -800,131 +768,94 @@ class Curve:
 
     def ecdsa_sign_msg(self, secret_d, msgs: Sequence[bytes], extra=None, flags: Optional[int] = None):
         """Signer::sign (extra=None) / RandomizedSigner::sign_with_rng (extra given) for a batch -> (sig_rs, recovery_id, ok)"""
+        return self._ecdsa_sign_msgs("ecgpu_ecdsa_sign_msg_batch", (), secret_d, msgs, extra, flags)
+
+    def _ecdsa_sign_msgs(self, name: str, hash_arg: tuple, secret_d, msgs, extra, flags):
+        """the message-level signing calls: on the curve's own digest (hash_arg empty) or on a chosen one (hash_arg = (hash_id,))"""
         d = _as_host(secret_d, self.nb)
         x = None if extra is None else _as_host(extra, self.nb)
-        if len(d) != len(msgs) or (x is not None and len(x) != len(d)):
-            raise ValueError("key, message and additional-data batches differ in length")
-        rec, lens, stride = pack_messages_aligned(msgs)
-        sig, rid, ok = _host_out(len(d), 2 * self.nb), np.zeros(len(d), dtype=np.uint8), np.zeros(len(d), dtype=np.uint8)
-        fl = self.default_ecdsa_flags() if flags is None else flags
-        self.ctx.check(self.ctx.lib.ecgpu_ecdsa_sign_msg_batch(self.ctx.handle, self.id, _ptr(d)[0], _ptr(rec)[0] if stride else None, stride, _ptr(lens)[0],
-                                                               _ptr(x)[0], _ptr(sig)[0], _ptr(rid)[0], _ptr(ok)[0], len(d), HOST, fl))
+        _equal_lengths("key, message and additional-data", d, msgs, x)
+        m = _host_messages(msgs)
+        sig, rid, ok = _host_out(len(d), 2 * self.nb), _host_flags(len(d)), _host_flags(len(d))
+        self._call(name, *hash_arg, d, *m, x, sig, rid, ok, len(d), HOST, self._flags(flags))
         return sig, rid, ok
 
     def ecdsa_sign_msg_device(self, d_secret, d_msgs, msg_stride: int, d_msg_len, d_extra, d_sig_rs, d_recid, d_ok, n: int, flags: Optional[int] = None):
-        fl = self.default_ecdsa_flags() if flags is None else flags
-        self.ctx.check(self.ctx.lib.ecgpu_ecdsa_sign_msg_batch(self.ctx.handle, self.id, _ptr(d_secret)[0], _ptr(d_msgs)[0], msg_stride, _ptr(d_msg_len)[0],
-                                                               _ptr(d_extra)[0], _ptr(d_sig_rs)[0], _ptr(d_recid)[0], _ptr(d_ok)[0], n, DEVICE, fl))
+        self._call("ecgpu_ecdsa_sign_msg_batch", d_secret, d_msgs, msg_stride, d_msg_len, d_extra, d_sig_rs, d_recid, d_ok, n, DEVICE, self._flags(flags))
 
     def ecdsa_verify_msg(self, msgs: Sequence[bytes], sig_rs, pubkeys_xy, flags: Optional[int] = None) -> np.ndarray:
         """Verifier::verify for a batch -> ok"""
+        return self._ecdsa_verify_msgs("ecgpu_ecdsa_verify_msg_batch", (), msgs, sig_rs, pubkeys_xy, flags)
+
+    def _ecdsa_verify_msgs(self, name: str, hash_arg: tuple, msgs, sig_rs, pubkeys_xy, flags):
         sg, q = _as_host(sig_rs, 2 * self.nb), _as_host(pubkeys_xy, 2 * self.nb)
-        if not (len(msgs) == len(sg) == len(q)):
-            raise ValueError("message, signature and public-key batches differ in length")
-        rec, lens, stride = pack_messages_aligned(msgs)
-        ok = np.zeros(len(sg), dtype=np.uint8)
-        fl = self.default_ecdsa_flags() if flags is None else flags
-        self.ctx.check(self.ctx.lib.ecgpu_ecdsa_verify_msg_batch(self.ctx.handle, self.id, _ptr(rec)[0] if stride else None, stride, _ptr(lens)[0], _ptr(sg)[0],
-                                                                 _ptr(q)[0], _ptr(ok)[0], len(sg), HOST, fl))
+        _equal_lengths("message, signature and public-key", msgs, sg, q)
+        m = _host_messages(msgs)
+        ok = _host_flags(len(sg))
+        self._call(name, *hash_arg, *m, sg, q, ok, len(sg), HOST, self._flags(flags))
         return ok
 
     def ecdsa_verify_msg_device(self, d_msgs, msg_stride: int, d_msg_len, d_sig_rs, d_pubkeys_xy, d_ok, n: int, flags: Optional[int] = None):
-        fl = self.default_ecdsa_flags() if flags is None else flags
-        self.ctx.check(self.ctx.lib.ecgpu_ecdsa_verify_msg_batch(self.ctx.handle, self.id, _ptr(d_msgs)[0], msg_stride, _ptr(d_msg_len)[0], _ptr(d_sig_rs)[0],
-                                                                 _ptr(d_pubkeys_xy)[0], _ptr(d_ok)[0], n, DEVICE, fl))
+        self._call("ecgpu_ecdsa_verify_msg_batch", d_msgs, msg_stride, d_msg_len, d_sig_rs, d_pubkeys_xy, d_ok, n, DEVICE, self._flags(flags))
 
     def ecdsa_recover_msg(self, msgs: Sequence[bytes], sig_rs, recovery_id, flags: Optional[int] = None):
         """VerifyingKey::recover_from_msg for a batch -> (pubkeys_xy, ok)"""
+        return self._ecdsa_recover_msgs("ecgpu_ecdsa_recover_msg_batch", (), msgs, sig_rs, recovery_id, flags)
+
+    def _ecdsa_recover_msgs(self, name: str, hash_arg: tuple, msgs, sig_rs, recovery_id, flags):
         sg = _as_host(sig_rs, 2 * self.nb)
         rid = np.ascontiguousarray(recovery_id, dtype=np.uint8).reshape(-1)
-        if not (len(msgs) == len(sg) == len(rid)):
-            raise ValueError("message, signature and recovery-id batches differ in length")
-        rec, lens, stride = pack_messages_aligned(msgs)
-        out, ok = _host_out(len(sg), 2 * self.nb), np.zeros(len(sg), dtype=np.uint8)
-        fl = self.default_ecdsa_flags() if flags is None else flags
-        self.ctx.check(self.ctx.lib.ecgpu_ecdsa_recover_msg_batch(self.ctx.handle, self.id, _ptr(rec)[0] if stride else None, stride, _ptr(lens)[0], _ptr(sg)[0],
-                                                                  _ptr(rid)[0], _ptr(out)[0], _ptr(ok)[0], len(sg), HOST, fl))
+        _equal_lengths("message, signature and recovery-id", msgs, sg, rid)
+        m = _host_messages(msgs)
+        out, ok = _host_out(len(sg), 2 * self.nb), _host_flags(len(sg))
+        self._call(name, *hash_arg, *m, sg, rid, out, ok, len(sg), HOST, self._flags(flags))
         return out, ok
 
     # --- DigestSigner / DigestVerifier / recover_from_digest: the message-level calls on a chosen digest of the field's size ---
     def ecdsa_sign_digest(self, hash_id: int, secret_d, msgs: Sequence[bytes], extra=None, flags: Optional[int] = None):
         """DigestSigner::sign_digest / sign_digest_recoverable (extra=None) / RandomizedDigestSigner (extra given) for a batch, the
         messages hashed with hash_id on the device -> (sig_rs, recovery_id, ok).  The RFC 6979 nonce keeps the curve's own hash."""
-        d = _as_host(secret_d, self.nb)
-        x = None if extra is None else _as_host(extra, self.nb)
-        if len(d) != len(msgs) or (x is not None and len(x) != len(d)):
-            raise ValueError("key, message and additional-data batches differ in length")
-        rec, lens, stride = pack_messages_aligned(msgs)
-        sig, rid, ok = _host_out(len(d), 2 * self.nb), np.zeros(len(d), dtype=np.uint8), np.zeros(len(d), dtype=np.uint8)
-        fl = self.default_ecdsa_flags() if flags is None else flags
-        self.ctx.check(self.ctx.lib.ecgpu_ecdsa_sign_digest_batch(self.ctx.handle, self.id, hash_id, _ptr(d)[0], _ptr(rec)[0] if stride else None, stride,
-                                                                  _ptr(lens)[0], _ptr(x)[0], _ptr(sig)[0], _ptr(rid)[0], _ptr(ok)[0], len(d), HOST, fl))
-        return sig, rid, ok
+        return self._ecdsa_sign_msgs("ecgpu_ecdsa_sign_digest_batch", (hash_id,), secret_d, msgs, extra, flags)
 
     def ecdsa_sign_digest_device(self, hash_id: int, d_secret, d_msgs, msg_stride: int, d_msg_len, d_extra, d_sig_rs, d_recid, d_ok, n: int,
                                  flags: Optional[int] = None):
-        fl = self.default_ecdsa_flags() if flags is None else flags
-        self.ctx.check(self.ctx.lib.ecgpu_ecdsa_sign_digest_batch(self.ctx.handle, self.id, hash_id, _ptr(d_secret)[0], _ptr(d_msgs)[0], msg_stride,
-                                                                  _ptr(d_msg_len)[0], _ptr(d_extra)[0], _ptr(d_sig_rs)[0], _ptr(d_recid)[0], _ptr(d_ok)[0], n, DEVICE, fl))
+        self._call("ecgpu_ecdsa_sign_digest_batch", hash_id, d_secret, d_msgs, msg_stride, d_msg_len, d_extra, d_sig_rs, d_recid, d_ok, n, DEVICE,
+                   self._flags(flags))
 
     def ecdsa_verify_digest(self, hash_id: int, msgs: Sequence[bytes], sig_rs, pubkeys_xy, flags: Optional[int] = None) -> np.ndarray:
         """DigestVerifier::verify_digest for a batch -> ok"""
-        sg, q = _as_host(sig_rs, 2 * self.nb), _as_host(pubkeys_xy, 2 * self.nb)
-        if not (len(msgs) == len(sg) == len(q)):
-            raise ValueError("message, signature and public-key batches differ in length")
-        rec, lens, stride = pack_messages_aligned(msgs)
-        ok = np.zeros(len(sg), dtype=np.uint8)
-        fl = self.default_ecdsa_flags() if flags is None else flags
-        self.ctx.check(self.ctx.lib.ecgpu_ecdsa_verify_digest_batch(self.ctx.handle, self.id, hash_id, _ptr(rec)[0] if stride else None, stride, _ptr(lens)[0],
-                                                                    _ptr(sg)[0], _ptr(q)[0], _ptr(ok)[0], len(sg), HOST, fl))
-        return ok
+        return self._ecdsa_verify_msgs("ecgpu_ecdsa_verify_digest_batch", (hash_id,), msgs, sig_rs, pubkeys_xy, flags)
 
     def ecdsa_verify_digest_device(self, hash_id: int, d_msgs, msg_stride: int, d_msg_len, d_sig_rs, d_pubkeys_xy, d_ok, n: int, flags: Optional[int] = None):
-        fl = self.default_ecdsa_flags() if flags is None else flags
-        self.ctx.check(self.ctx.lib.ecgpu_ecdsa_verify_digest_batch(self.ctx.handle, self.id, hash_id, _ptr(d_msgs)[0], msg_stride, _ptr(d_msg_len)[0],
-                                                                    _ptr(d_sig_rs)[0], _ptr(d_pubkeys_xy)[0], _ptr(d_ok)[0], n, DEVICE, fl))
+        self._call("ecgpu_ecdsa_verify_digest_batch", hash_id, d_msgs, msg_stride, d_msg_len, d_sig_rs, d_pubkeys_xy, d_ok, n, DEVICE, self._flags(flags))
 
     def ecdsa_recover_digest(self, hash_id: int, msgs: Sequence[bytes], sig_rs, recovery_id, flags: Optional[int] = None):
         """VerifyingKey::recover_from_digest for a batch -> (pubkeys_xy, ok)"""
-        sg = _as_host(sig_rs, 2 * self.nb)
-        rid = np.ascontiguousarray(recovery_id, dtype=np.uint8).reshape(-1)
-        if not (len(msgs) == len(sg) == len(rid)):
-            raise ValueError("message, signature and recovery-id batches differ in length")
-        rec, lens, stride = pack_messages_aligned(msgs)
-        out, ok = _host_out(len(sg), 2 * self.nb), np.zeros(len(sg), dtype=np.uint8)
-        fl = self.default_ecdsa_flags() if flags is None else flags
-        self.ctx.check(self.ctx.lib.ecgpu_ecdsa_recover_digest_batch(self.ctx.handle, self.id, hash_id, _ptr(rec)[0] if stride else None, stride, _ptr(lens)[0],
-                                                                     _ptr(sg)[0], _ptr(rid)[0], _ptr(out)[0], _ptr(ok)[0], len(sg), HOST, fl))
-        return out, ok
+        return self._ecdsa_recover_msgs("ecgpu_ecdsa_recover_digest_batch", (hash_id,), msgs, sig_rs, recovery_id, flags)
 
     def ecdsa_recover_digest_device(self, hash_id: int, d_msgs, msg_stride: int, d_msg_len, d_sig_rs, d_recid, d_pubkeys_xy, d_ok, n: int,
                                     flags: Optional[int] = None):
-        fl = self.default_ecdsa_flags() if flags is None else flags
-        self.ctx.check(self.ctx.lib.ecgpu_ecdsa_recover_digest_batch(self.ctx.handle, self.id, hash_id, _ptr(d_msgs)[0], msg_stride, _ptr(d_msg_len)[0],
-                                                                     _ptr(d_sig_rs)[0], _ptr(d_recid)[0], _ptr(d_pubkeys_xy)[0], _ptr(d_ok)[0], n, DEVICE, fl))
+        self._call("ecgpu_ecdsa_recover_digest_batch", hash_id, d_msgs, msg_stride, d_msg_len, d_sig_rs, d_recid, d_pubkeys_xy, d_ok, n, DEVICE,
+                   self._flags(flags))
 
     def schnorr_sign_msg(self, secret_keys, msgs: Sequence[bytes], aux_rands=None):
         """BIP340 Signer::try_sign (aux_rands=None: 32 zero bytes) / try_sign_with_rng over SHA256(msg) for a batch (secp256k1)
         -> (sig_rs, pubkeys_x, ok)"""
         d = _as_host(secret_keys, self.nb)
         a = None if aux_rands is None else _as_host(aux_rands, 32)
-        if len(d) != len(msgs) or (a is not None and len(a) != len(d)):
-            raise ValueError("key, message and aux_rand batches differ in length")
-        rec, lens, stride = pack_messages_aligned(msgs)
-        sig, px, ok = _host_out(len(d), 2 * self.nb), _host_out(len(d), self.nb), np.zeros(len(d), dtype=np.uint8)
-        self.ctx.check(self.ctx.lib.ecgpu_schnorr_sign_msg_batch(self.ctx.handle, self.id, _ptr(d)[0], _ptr(rec)[0] if stride else None, stride, _ptr(lens)[0],
-                                                                 _ptr(a)[0], _ptr(sig)[0], _ptr(px)[0], _ptr(ok)[0], len(d), HOST))
+        _equal_lengths("key, message and aux_rand", d, msgs, a)
+        m = _host_messages(msgs)
+        sig, px, ok = _host_out(len(d), 2 * self.nb), _host_out(len(d), self.nb), _host_flags(len(d))
+        self._call("ecgpu_schnorr_sign_msg_batch", d, *m, a, sig, px, ok, len(d), HOST)
         return sig, px, ok
 
     def schnorr_verify_msg(self, pubkeys_x, msgs: Sequence[bytes], sig_rs) -> np.ndarray:
         """BIP340 Verifier::verify over SHA256(msg) for a batch (secp256k1) -> ok"""
         x, sg = _as_host(pubkeys_x, self.nb), _as_host(sig_rs, 2 * self.nb)
-        if not (len(x) == len(sg) == len(msgs)):
-            raise ValueError("key, message and signature batches differ in length")
-        rec, lens, stride = pack_messages_aligned(msgs)
-        ok = np.zeros(len(x), dtype=np.uint8)
-        self.ctx.check(self.ctx.lib.ecgpu_schnorr_verify_msg_batch(self.ctx.handle, self.id, _ptr(x)[0], _ptr(rec)[0] if stride else None, stride, _ptr(lens)[0],
-                                                                   _ptr(sg)[0], _ptr(ok)[0], len(x), HOST))
+        _equal_lengths("key, message and signature", x, sg, msgs)
+        m = _host_messages(msgs)
+        ok = _host_flags(len(x))
+        self._call("ecgpu_schnorr_verify_msg_batch", x, *m, sg, ok, len(x), HOST)
         return ok
 
     # --- BIP340 batch verification: one equation per batch (include/ecgpu.h).  seed=None: the library draws one per call -------
@@ -937,46 +868,42 @@ class Curve:
             raise ValueError("the seed of a batch verification is 32 bytes")
         return np.frombuffer(seed, dtype=np.uint8)
 
-    def _schnorr_batch_host(self, fn, pubkeys_x, sig_rs, third, seed, flags: int):
+    def _schnorr_batch_host(self, name: str, pubkeys_x, sig_rs, third, seed, flags: int):
         x, sg, t = _as_host(pubkeys_x, self.nb), _as_host(sig_rs, 2 * self.nb), _as_host(third, 32)
-        if not (len(x) == len(sg) == len(t)):
-            raise ValueError("key, signature and challenge / prehash batches differ in length")
-        ok, all_valid, sd = np.zeros(len(x), dtype=np.uint8), ctypes.c_int(0), self._batch_seed(seed)
-        self.ctx.check(fn(self.ctx.handle, self.id, _ptr(x)[0], _ptr(sg)[0], _ptr(t)[0], _ptr(sd)[0], _ptr(ok)[0], ctypes.byref(all_valid), len(x), HOST, flags))
+        _equal_lengths("key, signature and challenge / prehash", x, sg, t)
+        ok, all_valid, sd = _host_flags(len(x)), ctypes.c_int(0), self._batch_seed(seed)
+        self._call(name, x, sg, t, sd, ok, ctypes.byref(all_valid), len(x), HOST, flags)
         return ok, bool(all_valid.value)
 
     def schnorr_batch_verify(self, pubkeys_x, sig_rs, challenges, seed=None, flags: int = 0):
         """BIP340 batch verification from the challenge hashes -> (ok, all_valid)"""
-        return self._schnorr_batch_host(self.ctx.lib.ecgpu_schnorr_batch_verify, pubkeys_x, sig_rs, challenges, seed, flags)
+        return self._schnorr_batch_host("ecgpu_schnorr_batch_verify", pubkeys_x, sig_rs, challenges, seed, flags)
 
     def schnorr_batch_verify_prehash(self, pubkeys_x, sig_rs, prehashes, seed=None, flags: int = 0):
         """BIP340 batch verification from the 32-byte digests -> (ok, all_valid); ok as schnorr_verify_prehash gives it"""
-        return self._schnorr_batch_host(self.ctx.lib.ecgpu_schnorr_batch_verify_prehash, pubkeys_x, sig_rs, prehashes, seed, flags)
+        return self._schnorr_batch_host("ecgpu_schnorr_batch_verify_prehash", pubkeys_x, sig_rs, prehashes, seed, flags)
 
     def schnorr_batch_verify_prehash_device(self, d_pubkeys_x, d_sig_rs, d_prehash, d_ok, n: int, seed=None, flags: int = 0):
         """device-resident batch (d_ok may be None with BATCH_VERDICT_ONLY) -> (d_ok, all_valid); the call synchronises the stream"""
         all_valid, sd = ctypes.c_int(0), self._batch_seed(seed)
-        self.ctx.check(self.ctx.lib.ecgpu_schnorr_batch_verify_prehash(self.ctx.handle, self.id, _ptr(d_pubkeys_x)[0], _ptr(d_sig_rs)[0], _ptr(d_prehash)[0],
-                                                                       _ptr(sd)[0], _ptr(d_ok)[0], ctypes.byref(all_valid), n, DEVICE, flags))
+        self._call("ecgpu_schnorr_batch_verify_prehash", d_pubkeys_x, d_sig_rs, d_prehash, sd, d_ok, ctypes.byref(all_valid), n, DEVICE, flags)
         return d_ok, bool(all_valid.value)
 
     def schnorr_batch_verify_msg(self, pubkeys_x, msgs: Sequence[bytes], sig_rs, seed=None, flags: int = 0):
         """BIP340 batch verification over SHA256(msg) -> (ok, all_valid)"""
         x, sg = _as_host(pubkeys_x, self.nb), _as_host(sig_rs, 2 * self.nb)
-        if not (len(x) == len(sg) == len(msgs)):
-            raise ValueError("key, message and signature batches differ in length")
-        rec, lens, stride = pack_messages_aligned(msgs)
-        ok, all_valid, sd = np.zeros(len(x), dtype=np.uint8), ctypes.c_int(0), self._batch_seed(seed)
-        self.ctx.check(self.ctx.lib.ecgpu_schnorr_batch_verify_msg(self.ctx.handle, self.id, _ptr(x)[0], _ptr(rec)[0] if stride else None, stride, _ptr(lens)[0],
-                                                                   _ptr(sg)[0], _ptr(sd)[0], _ptr(ok)[0], ctypes.byref(all_valid), len(x), HOST, flags))
+        _equal_lengths("key, message and signature", x, sg, msgs)
+        m = _host_messages(msgs)
+        ok, all_valid, sd = _host_flags(len(x)), ctypes.c_int(0), self._batch_seed(seed)
+        self._call("ecgpu_schnorr_batch_verify_msg", x, *m, sg, sd, ok, ctypes.byref(all_valid), len(x), HOST, flags)
         return ok, bool(all_valid.value)
 
     # --- synthetic inputs (device buffers) ---------------------------------------------------------
     def synth_scalars_device(self, d_out, n: int, seed: int, first_index: int = 0):
-        self.ctx.check(self.ctx.lib.ecgpu_synth_scalars(self.ctx.handle, self.id, seed, first_index, _ptr(d_out)[0], n))
+        self._call("ecgpu_synth_scalars", seed, first_index, d_out, n)
 
     def synth_points_device(self, d_out, n: int, seed: int, first_index: int = 0):
-        self.ctx.check(self.ctx.lib.ecgpu_synth_points(self.ctx.handle, self.id, seed, first_index, _ptr(d_out)[0], n))
+        self._call("ecgpu_synth_points", seed, first_index, d_out, n)
 
 
 GROUP_NO_RCCL = 1
@@ -1035,34 +962,33 @@ class Group:
         return self.lib.ecgpu_group_gather_path(self.handle).decode()
 
     def synchronize(self):
-        self.check(self.lib.ecgpu_group_synchronize(self.handle))
+        _call(self, "ecgpu_group_synchronize")
 
     def lincomb(self, curve, scalars, points, terms: int = 1, point_format: int = AFFINE, out_format: int = AFFINE, flags: int = 0, out=None, out_inf=None):
-        cid = CURVE_IDS[curve] if isinstance(curve, str) else int(curve)
+        cid = _curve_id(curve)
         nb = FIELD_BYTES[cid]
         s = _as_host(scalars, nb)
         n = len(s) // terms
-        pw, ow = (3 if point_format == PROJECTIVE else 2) * nb, (3 if out_format == PROJECTIVE else 2) * nb
-        p = _as_host(points, pw) if points is not None else None
+        p = _as_host(points, _point_bytes(point_format, nb)) if points is not None else None
         if len(s) % terms or (p is not None and len(p) != n * terms):
             raise ValueError("scalars and points differ in count")
-        out = _host_out(n, ow) if out is None else out
-        inf = np.zeros(n, dtype=np.uint8) if out_inf is None else out_inf
-        self.check(self.lib.ecgpu_group_lincomb_batch(self.handle, cid, _ptr(s)[0], _ptr(p)[0], point_format, terms, _ptr(out)[0], out_format, _ptr(inf)[0], n, flags))
+        out = _host_out(n, _point_bytes(out_format, nb)) if out is None else out
+        inf = _host_flags(n) if out_inf is None else out_inf
+        _call(self, "ecgpu_group_lincomb_batch", cid, s, p, point_format, terms, out, out_format, inf, n, flags)
         return (out, inf) if out_format == AFFINE else out
 
     def mul(self, curve, scalars, points, **kw):
         return self.lincomb(curve, scalars, points, 1, **kw)
 
     def msm(self, curve, scalars, points, point_format: int = AFFINE, out_format: int = AFFINE) -> np.ndarray:
-        cid = CURVE_IDS[curve] if isinstance(curve, str) else int(curve)
+        cid = _curve_id(curve)
         nb = FIELD_BYTES[cid]
         s = _as_host(scalars, nb)
-        p = _as_host(points, (3 if point_format == PROJECTIVE else 2) * nb)
+        p = _as_host(points, _point_bytes(point_format, nb))
         if len(p) != len(s):
             raise ValueError("scalars and points differ in count")
-        out = _host_out(1, (3 if out_format == PROJECTIVE else 2) * nb)
-        self.check(self.lib.ecgpu_group_msm(self.handle, cid, _ptr(s)[0], _ptr(p)[0], point_format, len(s), _ptr(out)[0], out_format))
+        out = _host_out(1, _point_bytes(out_format, nb))
+        _call(self, "ecgpu_group_msm", cid, s, p, point_format, len(s), out, out_format)
         return out[0]
 
     @staticmethod
@@ -1072,16 +998,13 @@ class Group:
     def lincomb_sharded(self, curve, d_scalars, d_points, d_out, counts, terms: int = 1, point_format: int = AFFINE, out_format: int = AFFINE, d_out_inf=None,
                         flags: int = 0):
         """device-resident shards (lists of torch tensors / device pointers, one per member); asynchronous: Group.synchronize()"""
-        cid = CURVE_IDS[curve] if isinstance(curve, str) else int(curve)
         cnt = (ctypes.c_size_t * self.size)(*counts)
-        self.check(self.lib.ecgpu_group_lincomb_sharded(self.handle, cid, self._ptr_array(d_scalars), self._ptr_array(d_points) if d_points is not None else None,
-                                                        point_format, terms, self._ptr_array(d_out), out_format,
-                                                        self._ptr_array(d_out_inf) if d_out_inf is not None else None, cnt, flags))
+        _call(self, "ecgpu_group_lincomb_sharded", _curve_id(curve), self._ptr_array(d_scalars), self._ptr_array(d_points) if d_points is not None else None,
+                   point_format, terms, self._ptr_array(d_out), out_format, self._ptr_array(d_out_inf) if d_out_inf is not None else None, cnt, flags)
 
     def msm_sharded(self, curve, d_scalars, d_points, counts, point_format: int = AFFINE, out_format: int = AFFINE) -> np.ndarray:
-        cid = CURVE_IDS[curve] if isinstance(curve, str) else int(curve)
-        nb = FIELD_BYTES[cid]
+        cid = _curve_id(curve)
         cnt = (ctypes.c_size_t * self.size)(*counts)
-        out = _host_out(1, (3 if out_format == PROJECTIVE else 2) * nb)
-        self.check(self.lib.ecgpu_group_msm_sharded(self.handle, cid, self._ptr_array(d_scalars), self._ptr_array(d_points), point_format, cnt, _ptr(out)[0], out_format))
+        out = _host_out(1, _point_bytes(out_format, FIELD_BYTES[cid]))
+        _call(self, "ecgpu_group_msm_sharded", cid, self._ptr_array(d_scalars), self._ptr_array(d_points), point_format, cnt, out, out_format)
         return out[0]

@@ -113,10 +113,10 @@ def recover_digest(curve: Curve, hash_id: int, messages: Sequence[bytes], sigs_r
 def eth_addresses(ctx, pubkeys_xy) -> np.ndarray:
     """Ethereum addresses of secp256k1 public keys: the last 20 bytes of Keccak-256 over each 64-byte x || y (what a caller of
     recovery wants) -> (n, 20).  It is ecgpu_digest_batch on the records as they lie, 64 bytes apart, and a slice."""
-    from . import HOST, KECCAK256, _as_host, _host_out, _ptr
+    from . import HOST, KECCAK256, _as_host, _call, _host_out
     q = _as_host(pubkeys_xy, 64)
     out = _host_out(len(q), 32)
-    ctx.check(ctx.lib.ecgpu_digest_batch(ctx.handle, KECCAK256, _ptr(q)[0], 64, None, _ptr(out)[0], len(q), HOST))
+    _call(ctx, "ecgpu_digest_batch", KECCAK256, q, 64, None, out, len(q), HOST)
     return np.ascontiguousarray(out[:, 12:])
 
 
