@@ -118,7 +118,41 @@ enum {
    * Precondition, as for the reference's types: the points are points of the curve.  ecgpu_mul_batch does not validate them (ecgpu_validate_points /
    * ecgpu_ecdh_batch do); for a point that is NOT on the curve the element's own result is unspecified, but it cannot disturb any other element of the
    * batch (a zero denominator is flagged and kept out of the shared inversions), and the instruction stream does not depend on it. */
-  ECGPU_SECRET_SCALARS = 8u
+  ECGPU_SECRET_SCALARS = 8u,
+  /* (16 and 32 are the BIP340 batch calls' ECGPU_BATCH_* flags.)
+   * ecgpu_mul_batch / ecgpu_lincomb_batch and their _checked forms: `points` holds `terms` points that EVERY element uses,
+   *   out[i] = sum_j scalars[i * terms + j] * points[j],
+   * the shape of verification under one key, Pedersen commitments a G + r H, ElGamal / ECIES to one recipient.  The flag never
+   * changes what is computed: the result is byte for byte that of the same call with the points replicated n times; it only lets the
+   * library multiply from a cached digit-indexed table of each point, as it does for the generator (no doublings).
+   *   - `points` is in HOST memory whatever `mem` says (as `dst` of the hash-to-curve calls is): its bytes are the cache key, and a
+   *     hit costs no copy and no synchronisation.  Its format must be ECGPU_PT_AFFINE (a projective point has many encodings);
+   *     ECGPU_PT_PROJECTIVE with the flag is ECGPU_ERR_ARG.
+   *   - Unless every point's table is already cached, the points are validated on the device (coordinates below p, on the curve; the
+   *     all-zero identity is allowed and its term contributes nothing): a point that fails makes the call return ECGPU_ERR_ARG with its
+   *     index in ecgpu_last_error, and nothing is written.
+   *   - Table path: up to 8 terms, not ECGPU_EXACT_REFERENCE; one term runs on the generator's own kernels with the point's table,
+   *     2 .. 8 terms on one kernel that adds all terms' entries into one accumulator (csrc/sharedbase.hpp).  With
+   *     ECGPU_SECRET_SCALARS and one term the constant-time fixed-base kernel runs on a 5-bit table of the point.
+   *   - Broadcast path, always available: the points are replicated into a workspace and the ordinary call runs on them.  It serves
+   *     ECGPU_EXACT_REFERENCE (whose (X, Y, Z) is that of the reference schedule), more than 8 terms, ECGPU_SECRET_SCALARS with more
+   *     than one term or the identity as the point, and batches too small to pay for a table that is not cached yet.
+   *   - Tables live in the context: up to 16 per curve, least recently used out first, within ECGPU_OPT_SHARED_TABLE_BUDGET bytes
+   *     over all curves; a table that does not fit (the budget, or hipErrorOutOfMemory) is built one width narrower (20 -> 16 -> 8).
+   *     All the tables of one call have one width, chosen before anything is built so that they fit the budget together.
+   *   - Size rule, measured (profiles/shared_points.txt; one point, device-resident, against the replicated call).  A cached table
+   *     is used at any size: 3-5 times the replicated call at 2^10 results, 8-18 times at 2^22.  A point without a table gets one
+   *     only from the batch size at which build plus call beat the replicated call by more than the spread of the runs: 2^20
+   *     results on secp256k1, 2^18 on P-256 and P-384 (ECGPU_OPT_SHARED_MIN; a build takes 1.7 ms, 1.6 ms, 5.2 ms with 8-bit
+   *     windows).  Below that the call takes the broadcast path.  The width built: 8-bit windows, 16-bit from 2^20 results (2^22 on
+   *     P-384), where their build and call beat the 8-bit table's.  20-bit windows do not pay for their build within 2^22 results
+   *     (secp256k1: 6.8 ms against 5.4 ms), so only ECGPU_OPT_SHARED_WINDOW builds them; once cached they are the fastest.
+   * ecgpu_ecdsa_verify_batch: `pubkeys_xy` is ONE key, in host memory, that all n signatures are checked against (u2 Q runs on the
+   * key's table); an invalid key gives ok[i] = 0 for every i and no error, as for the per-element call.
+   * Every other entry point that takes per-element points or keys and a flags word refuses the flag with ECGPU_ERR_UNSUPPORTED
+   * (ecgpu_group_mul_batch, ecgpu_group_lincomb_batch, ecgpu_group_lincomb_sharded, ecgpu_ecdsa_verify_msg_batch,
+   * ecgpu_ecdsa_verify_digest_batch): a short buffer must never be read as n points. */
+  ECGPU_SHARED_POINTS = 64u
 };
 
 /* ---- context ------------------------------------------------------------------------------
@@ -166,7 +200,17 @@ typedef enum ecgpu_option {
   ECGPU_OPT_LINCOMB_TERM_BY_TERM = 8, /* 1: combinations of 3 .. 1024 terms run as one reference-schedule multiplication per term folded with
                                      the complete addition (the form used until round 4: measurements, cross-checks), 0: the shared-doubling
                                      schedule of csrc/straus.hpp [0] */
-  ECGPU_OPT_COUNT_ = 9
+  /* tables of shared points (ECGPU_SHARED_POINTS) */
+  ECGPU_OPT_SHARED_WINDOW = 9,    /* pin the window width of shared-point tables: 8 | 16 | 20, 0 = by batch size [0] */
+  ECGPU_OPT_SHARED_MIN = 10,      /* smallest batch that builds a table for a point that has none: 0 = the default (2^20 on secp256k1,
+                                     2^18 on P-256 / P-384: measured),
+                                     1 = always, any other value = that many results [0] */
+  ECGPU_OPT_SHARED_TABLE_BUDGET = 11, /* bytes of device memory the shared-point tables of ALL curves may take in this context [2^31];
+                                     a table that would exceed it evicts the least recently used ones; a call whose tables do not fit together
+                                     is built one width narrower */
+  ECGPU_OPT_SHARED_TABLE_BUILDS = 12, /* read: shared-point tables built so far in this context (hits build nothing, misses and
+                                     rebuilds after an eviction count); set accepts only 0, which resets the counter */
+  ECGPU_OPT_COUNT_ = 13
 } ecgpu_option;
 int ecgpu_set_option(ecgpu_ctx* ctx, int option, int64_t value);
 int ecgpu_get_option(ecgpu_ctx* ctx, int option, int64_t* value);

@@ -162,13 +162,18 @@ struct CurveOps {
   static int mul_gen_wide(ecgpu_ctx* c, void** slot, const u32* sc, u32* out, int out_fmt, uint8_t* out_inf, size_t n) {
     int rc = ensure_fb_wide_table<WB>(c, slot);
     if (rc) return rc;
+    return mul_wide_table<WB>(c, *slot, sc, out, out_fmt, out_inf, n);
+  }
+  // the wide kernel on any table of its layout: the generator's, or a shared point's (sharedbase.hpp)
+  template <int WB>
+  static int mul_wide_table(ecgpu_ctx* c, const void* table, const u32* sc, u32* out, int out_fmt, uint8_t* out_inf, size_t n) {
     unsigned long long* ctr = ecgpu_sched_counter(c);
     if (!ctr) return ECGPU_ERR_RUNTIME;
     // a chunk of 0 results never advances the work counter (the kernel hangs); one above the batch overruns the result buffer before its flush test
     static_assert(FB_CHUNK_UNITS >= 1 && FB_CHUNK_UNITS <= (FB_BATCH), "FB_CHUNK_UNITS must lie in 1 .. FB_BATCH");
     const unsigned grid = ecgpu_grid_for(c, n, FB_WIDE_WAVES);
     hipLaunchKernelGGL((fb::mul_wide_kernel<C, WB, FB_BATCH, FB_WIDE_WAVES>), dim3(grid), dim3(256), 0, c->stream, sc,
-                       (const AffEntry<C>*)*slot, out, out_fmt, out_inf, n, WaveSched{ctr, (unsigned long long)n, grid * 4u, (unsigned)FB_CHUNK_UNITS, 1u});
+                       (const AffEntry<C>*)table, out, out_fmt, out_inf, n, WaveSched{ctr, (unsigned long long)n, grid * 4u, (unsigned)FB_CHUNK_UNITS, 1u});
     HIPCHK(c, hipGetLastError());
     return 1;
   }
@@ -206,15 +211,91 @@ struct CurveOps {
     int rc = ensure_fb_wide_table<fb::CT_WB>(c, &c->table[ECGPU_TAB_FBCT][C::ID]);
     if (rc == FB_NOMEM) return ecgpu_set_err(c, ECGPU_ERR_RUNTIME, "hipMalloc failed (out of device memory) for the 5-bit generator table of the constant-time kernel");
     if (rc) return rc;
+    return mul_ct_table(c, c->table[ECGPU_TAB_FBCT][C::ID], sc, out, out_fmt, out_inf, n);
+  }
+  // the constant-time kernel on any 5-bit table: the generator's, or a shared point's (fixedbase_ct.hpp: the argument needs the base's order only)
+  static int mul_ct_table(ecgpu_ctx* c, const void* table, const u32* sc, u32* out, int out_fmt, uint8_t* out_inf, size_t n) {
     if constexpr (C::ID == 0) {          // secp256k1: the kernel lives in the branch-free translation unit (ops_k256_ct.hip)
-      return ecgpuint_k256_mul_gen_ct(c, sc, c->table[ECGPU_TAB_FBCT][C::ID], out, out_fmt, out_inf, n);
+      return ecgpuint_k256_mul_gen_ct(c, sc, table, out, out_fmt, out_inf, n);
     } else {
       constexpr int WAVES = FBCT_WAVES(C);
-      hipLaunchKernelGGL((fb::mul_ct_kernel<C, 8, WAVES>), dim3(ecgpu_grid_oversubscribed(c, n, WAVES, 8, FBCT_GRID_MULT)), dim3(256), 0, c->stream, sc, (const AffEntry<C>*)c->table[ECGPU_TAB_FBCT][C::ID], out,
+      hipLaunchKernelGGL((fb::mul_ct_kernel<C, 8, WAVES>), dim3(ecgpu_grid_oversubscribed(c, n, WAVES, 8, FBCT_GRID_MULT)), dim3(256), 0, c->stream, sc, (const AffEntry<C>*)table, out,
                          out_fmt, out_inf, n);
       HIPCHK(c, hipGetLastError());
       return 0;
     }
+  }
+  // ---- shared points (sharedbase.hpp): the launchers behind ECGPU_SHARED_POINTS; which table a call uses is the API layer's business
+  static_assert(fb::SHARED_MAX_TERMS == ECGPU_SHARED_MAX_TERMS, "the API layer plans for as many tables as one launch reads");
+  static size_t shared_table_bytes(int wb) {
+    switch (wb) {
+      case fb::CT_WB: return sizeof(AffEntry<C>) * (size_t)fb::nwin_wide<C, fb::CT_WB>() * fb::wide_entries<fb::CT_WB>();
+      case 8: return sizeof(AffEntry<C>) * (size_t)fb::nwin_wide<C, 8>() * fb::wide_entries<8>();
+      case 16: return sizeof(AffEntry<C>) * (size_t)fb::nwin_wide<C, 16>() * fb::wide_entries<16>();
+      case 20: return sizeof(AffEntry<C>) * (size_t)fb::nwin_wide<C, 20>() * fb::wide_entries<20>();
+      default: return 0;
+    }
+  }
+  template <int WB>
+  static int shared_build_w(ecgpu_ctx* c, const u32* xy, void* bases, void* table) {
+    constexpr int NWIN = fb::nwin_wide<C, WB>();
+    const size_t runs = (size_t)NWIN * (fb::wide_entries<WB>() / fb::SHARED_RUN);
+    hipLaunchKernelGGL((fb::shared_bases_kernel<C, WB>), dim3((NWIN + 63) / 64), dim3(64), 0, c->stream, xy, (AffEntry<C>*)bases);
+    hipLaunchKernelGGL((fb::shared_runs_kernel<C, WB>), dim3(ecgpu_grid_for(c, runs, 8)), dim3(256), 0, c->stream, (const AffEntry<C>*)bases,
+                       (AffEntry<C>*)table, runs);
+    HIPCHK(c, hipGetLastError());
+    return 0;
+  }
+  static int shared_build(ecgpu_ctx* c, const u32* xy, int wb, void* bases, void* table) {
+    switch (wb) {
+      case fb::CT_WB: return shared_build_w<fb::CT_WB>(c, xy, bases, table);
+      case 8: return shared_build_w<8>(c, xy, bases, table);
+      case 16: return shared_build_w<16>(c, xy, bases, table);
+      case 20: return shared_build_w<20>(c, xy, bases, table);
+      default: return ecgpu_set_err(c, ECGPU_ERR_ARG, "shared points: no table of %d-bit windows", wb);
+    }
+  }
+  template <int WB>
+  static int shared_lincomb_w(ecgpu_ctx* c, const u32* sc, const void* const* tables, size_t terms, u32* out, int out_fmt, uint8_t* out_inf, size_t n) {
+    fb::SharedTabs<C> tabs;
+    for (int t = 0; t < fb::SHARED_MAX_TERMS; t++) tabs.t[t] = t < (int)terms ? (const AffEntry<C>*)tables[t] : nullptr;
+    tabs.terms = (int)terms;
+    unsigned long long* ctr = ecgpu_sched_counter(c);
+    if (!ctr) return ECGPU_ERR_RUNTIME;
+    const unsigned grid = ecgpu_grid_for(c, n, FB_WIDE_WAVES);
+    hipLaunchKernelGGL((fb::mul_shared_kernel<C, WB, FB_BATCH, FB_WIDE_WAVES>), dim3(grid), dim3(256), 0, c->stream, sc, tabs, out, out_fmt, out_inf, n,
+                       WaveSched{ctr, (unsigned long long)n, grid * 4u, (unsigned)FB_CHUNK_UNITS, 1u});
+    HIPCHK(c, hipGetLastError());
+    return 0;
+  }
+  static int shared_lincomb(ecgpu_ctx* c, const u32* sc, const void* const* tables, int wb, size_t terms, u32* out, int out_fmt, uint8_t* out_inf, size_t n,
+                            unsigned flags) {
+    if (terms < 1 || terms > (size_t)fb::SHARED_MAX_TERMS) return ecgpu_set_err(c, ECGPU_ERR_ARG, "shared points: 1 .. %d tables per launch", fb::SHARED_MAX_TERMS);
+    if (flags & ECGPU_SECRET_SCALARS) {
+      if (terms != 1 || wb != fb::CT_WB || !tables[0]) return ecgpu_set_err(c, ECGPU_ERR_ARG, "shared points: secret scalars take one 5-bit table");
+      return mul_ct_table(c, tables[0], sc, out, out_fmt, out_inf, n);
+    }
+    // one table: the generator's kernels, unchanged (a positive return is their "launched")
+    if (terms == 1 && tables[0]) {
+      if (wb == 20) { int rc = mul_wide_table<20>(c, tables[0], sc, out, out_fmt, out_inf, n); return rc < 0 ? rc : 0; }
+      if (wb == 16) { int rc = mul_wide_table<16>(c, tables[0], sc, out, out_fmt, out_inf, n); return rc < 0 ? rc : 0; }
+      if (wb == 8) {
+        hipLaunchKernelGGL((fb::mul_kernel<C, 16, 4>), dim3(ecgpu_grid_for(c, n, 4)), dim3(256), 0, c->stream, sc, (const AffEntry<C>*)tables[0], out, out_fmt, out_inf, n);
+        HIPCHK(c, hipGetLastError());
+        return 0;
+      }
+    }
+    switch (wb) {
+      case 8: return shared_lincomb_w<8>(c, sc, tables, terms, out, out_fmt, out_inf, n);
+      case 16: return shared_lincomb_w<16>(c, sc, tables, terms, out, out_fmt, out_inf, n);
+      case 20: return shared_lincomb_w<20>(c, sc, tables, terms, out, out_fmt, out_inf, n);
+      default: return ecgpu_set_err(c, ECGPU_ERR_ARG, "shared points: no kernel for %d-bit windows", wb);
+    }
+  }
+  static int broadcast_points(ecgpu_ctx* c, const u32* xy, size_t terms, u32* dst, size_t n) {
+    hipLaunchKernelGGL((fb::broadcast_points_kernel<C>), dim3(ecgpu_grid_for(c, n * terms * 2 * C::NW, 8)), dim3(256), 0, c->stream, xy, terms * 2 * C::NW, dst, n);
+    HIPCHK(c, hipGetLastError());
+    return 0;
   }
   // curve-specific throughput kernels hook in here (specialised in ops_*.hip); returns 1 if it launched
   static int lincomb_fast(ecgpu_ctx* c, const u32* sc, const u32* pts, int pt_fmt, size_t terms, u32* out, int out_fmt,
@@ -393,6 +474,23 @@ struct CurveOps {
     hipLaunchKernelGGL((ecdsa::verify_prep_kernel<C, 16>), dim3(ecgpu_grid_for(c, (n + 15) / 16, 4)), dim3(256), 0, c->stream, z, sig, q, w.u1, w.u2,
                        ok, n, flags);
     if ((rc = verify_products(c, w, q, n))) return rc;
+    hipLaunchKernelGGL((ecdsa::verify_check_kernel<C>), dim3(ecgpu_grid_for(c, n, 8)), dim3(256), 0, c->stream, (const u32*)w.a,
+                       (const uint8_t*)w.a_inf, (const u32*)w.b, (const uint8_t*)w.b_inf, sig, ok, n);
+    HIPCHK(c, hipGetLastError());
+    return 0;
+  }
+  // ecdsa_verify against ONE valid key Q: q_rep holds Q n times, so the prep kernel computes what it computes for a per-element
+  // call; a = u1 G as there, b = u2 Q from Q's table
+  static int ecdsa_verify_shared(ecgpu_ctx* c, const u32* z, const u32* sig, const u32* q_rep, const void* table, int wb, uint8_t* ok, size_t n,
+                                 unsigned flags) {
+    VerifyWs w;
+    int rc = verify_ws(c, n, false, w);
+    if (rc) return rc;
+    hipLaunchKernelGGL((ecdsa::verify_prep_kernel<C, 16>), dim3(ecgpu_grid_for(c, (n + 15) / 16, 4)), dim3(256), 0, c->stream, z, sig, q_rep, w.u1, w.u2,
+                       ok, n, flags);
+    HIPCHK(c, hipGetLastError());
+    if ((rc = lincomb(c, w.u1, nullptr, FMT_AFFINE, 1, w.a, FMT_AFFINE, w.a_inf, n, 0))) return rc;
+    if ((rc = shared_lincomb(c, w.u2, &table, wb, 1, w.b, FMT_AFFINE, w.b_inf, n, 0))) return rc;
     hipLaunchKernelGGL((ecdsa::verify_check_kernel<C>), dim3(ecgpu_grid_for(c, n, 8)), dim3(256), 0, c->stream, (const u32*)w.a,
                        (const uint8_t*)w.a_inf, (const u32*)w.b, (const uint8_t*)w.b_inf, sig, ok, n);
     HIPCHK(c, hipGetLastError());
@@ -631,7 +729,8 @@ struct CurveOps {
     static const ecgpu_curve_ops t = {field_op, point_op, point_eq, normalize, lincomb, msm, validate_scalars, validate_points,
                                       decompress, synth_scalars, synth_points, to_bytes, from_bytes, sec1_encode, sec1_decode, ecdsa_verify, h2c_map, ecdsa_recover, schnorr_verify, ecdsa_sign, ecdh,
                                       pass_units, scalar_op, scalar_reduce, h2c_hash_to_field, field_from_okm, schnorr_challenge,
-                                      rfc6979_nonce, ecdsa_sign_prehash, schnorr_sign_prehash, schnorr_batch_verify};
+                                      rfc6979_nonce, ecdsa_sign_prehash, schnorr_sign_prehash, schnorr_batch_verify,
+                                      shared_table_bytes, shared_build, shared_lincomb, broadcast_points, ecdsa_verify_shared};
     return &t;
   }
 };

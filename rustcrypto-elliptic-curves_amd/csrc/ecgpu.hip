@@ -176,7 +176,7 @@ static const ecgpu_curve_ops* ops_for(int curve) {
 
 extern "C" {
 
-const char* ecgpu_version(void) { return "ecgpu 0.10 (gfx950)"; }
+const char* ecgpu_version(void) { return "ecgpu 0.11 (gfx950)"; }
 
 size_t ecgpu_field_bytes(int curve) {
   switch (curve) {
@@ -241,7 +241,8 @@ void ecgpu_destroy(ecgpu_ctx* c) {
   for (auto& kind : c->table)
     for (void* t : kind)
       if (t) (void)hipFree(t);
-  for (DevBuf* b : {&c->msm_ws, &c->tab_ws, &c->ecdsa_ws, &c->hash_ws})
+  for (const ecgpu_ctx::SharedTable& t : c->shared_tabs) (void)hipFree(t.p);
+  for (DevBuf* b : {&c->msm_ws, &c->tab_ws, &c->ecdsa_ws, &c->hash_ws, &c->shared_ws})
     if (b->p) (void)hipFree(b->p);
   if (c->sched_ctr) (void)hipFree(c->sched_ctr);
   if (c->ev0) (void)hipEventDestroy(c->ev0);
@@ -307,6 +308,10 @@ int ecgpu_set_option(ecgpu_ctx* c, int option, int64_t v) {
     case ECGPU_OPT_K256_WAVES: ok = (v == 3 || v == 4); break;
     case ECGPU_OPT_FB_MEMORY_BUDGET: ok = (v >= 0); break;
     case ECGPU_OPT_LINCOMB_TERM_BY_TERM: ok = (v == 0 || v == 1); break;
+    case ECGPU_OPT_SHARED_WINDOW: ok = (v == 0 || v == 8 || v == 16 || v == 20); break;
+    case ECGPU_OPT_SHARED_MIN: ok = (v >= 0); break;
+    case ECGPU_OPT_SHARED_TABLE_BUDGET: ok = (v >= 0); break;
+    case ECGPU_OPT_SHARED_TABLE_BUILDS: ok = (v == 0); break;       // a counter: it can only be reset
     default: return ecgpu_set_err(c, ECGPU_ERR_ARG, "ecgpu_set_option: unknown option %d", option);
   }
   if (!ok) return ecgpu_set_err(c, ECGPU_ERR_ARG, "ecgpu_set_option: value %lld is not allowed for option %d", (long long)v, option);
@@ -474,15 +479,240 @@ int ecgpu_batch_normalize(ecgpu_ctx* c, int curve, const uint8_t* p, uint8_t* ou
   });
 }
 
+// ---------------------------------------------------------------------------------------------
+// Shared points (include/ecgpu.h, ECGPU_SHARED_POINTS): `terms` host points that every element of the batch uses.  shared_prepare decides
+// between the table path (every point's table in the context's cache, built on a miss; csrc/sharedbase.hpp) and the broadcast path (the
+// points replicated in shared_ws for the ordinary launchers) and leaves the call's Plan; everything runs under the context lock the
+// entry point holds, and before run_batch: a build and an eviction synchronise the stream.
+// ---------------------------------------------------------------------------------------------
+namespace shared {
+// The size rule, from measurements (profiles/shared_points.txt; one point, device-resident, against the replicated call).
+// default_min: the smallest measured batch at which a first call - build and multiplication - beats the replicated call by more than the
+// spread of the runs.  rule_width: the width a miss builds - 16-bit windows from the size at which their build and call beat the 8-bit
+// table's; 20-bit windows do not pay for their build within 2^22 results, so a miss never picks them (ECGPU_OPT_SHARED_WINDOW does, and
+// a cached 20-bit table is used at every size).
+static size_t default_min(int curve) { return (size_t)1 << (curve == ECGPU_K256 ? 20 : 18); }
+static int rule_width(int curve, size_t n) { return n >= ((size_t)1 << (curve == ECGPU_P384 ? 22 : 20)) ? 16 : 8; }
+constexpr int NOMEM = 100;                          // internal: a table did not fit, the caller steps down a width
+constexpr int CT_WB = 5;                            // the constant-time kernel's table (fixedbase_ct.hpp)
+struct Plan {
+  bool table = false;                               // the table path; otherwise `rep` holds the points for the ordinary launchers
+  int wb = 0;
+  const void* tabs[ECGPU_SHARED_MAX_TERMS] = {};    // nullptr: that term's point is the identity
+  uint32_t* rep = nullptr;                          // the points n times: the broadcast path, and a shared key for its prep kernel
+  bool valid = true;                                // a shared key that failed validation: the call's answer is all zeros, not an error
+};
+static bool is_identity(const uint8_t* p, size_t bytes) {
+  uint8_t z = 0;
+  for (size_t i = 0; i < bytes; i++) z |= p[i];
+  return z == 0;
+}
+static ecgpu_ctx::SharedTable* find(ecgpu_ctx* c, int curve, const uint8_t* key, size_t kb, int wb) {
+  for (ecgpu_ctx::SharedTable& t : c->shared_tabs)
+    if (t.curve == curve && t.wb == wb && memcmp(t.key, key, kb) == 0) return &t;
+  return nullptr;
+}
+// the point's canonical words, kept behind its table
+static const uint32_t* words_of(const ecgpu_ctx::SharedTable& t) { return (const uint32_t*)((const char*)t.p + t.bytes); }
+// Frees the least recently used table that this call (`clock`) does not use - of `curve`, or of any curve for curve < 0.  The stream is
+// drained first: a kernel of an earlier call may still read the table.
+static int evict_one(ecgpu_ctx* c, int curve, uint64_t clock) {
+  size_t victim = c->shared_tabs.size();
+  for (size_t i = 0; i < c->shared_tabs.size(); i++) {
+    const ecgpu_ctx::SharedTable& t = c->shared_tabs[i];
+    if (t.used == clock || (curve >= 0 && t.curve != curve)) continue;
+    if (victim == c->shared_tabs.size() || t.used < c->shared_tabs[victim].used) victim = i;
+  }
+  if (victim == c->shared_tabs.size()) return NOMEM;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipFree(c->shared_tabs[victim].p));
+  c->shared_bytes -= c->shared_tabs[victim].bytes;
+  c->shared_tabs.erase(c->shared_tabs.begin() + victim);
+  return 0;
+}
+// *table = the table of width wb of the point `key` (its words are at d_xy on the device), from the cache or built now.
+static int ensure(ecgpu_ctx* c, const ecgpu_curve_ops* ops, int curve, const uint8_t* key, size_t kb, int wb, const uint32_t* d_xy, void* bases,
+                  uint64_t clock, const void** table) {
+  if (ecgpu_ctx::SharedTable* t = find(c, curve, key, kb, wb)) {
+    t->used = clock;
+    *table = t->p;
+    return 0;
+  }
+  const size_t bytes = ops->shared_table_bytes(wb);
+  if (!bytes) return ecgpu_set_err(c, ECGPU_ERR_ARG, "shared points: no table of %d-bit windows", wb);
+  // (like the generator's, the 5-bit table of the constant-time kernel - 53-116 KB - is never refused on the budget's account, though it counts)
+  const size_t budget = (size_t)c->opt[ECGPU_OPT_SHARED_TABLE_BUDGET];
+  const bool budgeted = wb != CT_WB;
+  if (budgeted && bytes > budget) return NOMEM;
+  for (;;) {
+    size_t of_curve = 0;
+    for (const ecgpu_ctx::SharedTable& t : c->shared_tabs) of_curve += t.curve == curve;
+    int rc;
+    if (of_curve >= ecgpu_ctx::SHARED_TABLES_PER_CURVE) rc = evict_one(c, curve, clock);
+    else if (budgeted && c->shared_bytes + bytes > budget) rc = evict_one(c, -1, clock);
+    else break;
+    if (rc) return rc;
+  }
+  void* p = nullptr;
+  for (;;) {
+    const hipError_t e = hipMalloc(&p, bytes + kb);
+    if (e == hipSuccess) break;
+    if (e != hipErrorOutOfMemory) return ecgpu_set_err(c, ECGPU_ERR_RUNTIME, "shared-point table (%d-bit windows): %s", wb, hipGetErrorString(e));
+    (void)hipGetLastError();           // not sticky: the next launch check must not report it
+    const int rc = evict_one(c, -1, clock);
+    if (rc) return rc;                 // nothing left to free: the caller steps down a width
+  }
+  int rc = ops->shared_build(c, d_xy, wb, bases, p);
+  hipError_t e = rc ? hipSuccess : hipMemcpyAsync((char*)p + bytes, d_xy, kb, hipMemcpyDeviceToDevice, c->stream);
+  if (!rc && e == hipSuccess) e = hipStreamSynchronize(c->stream);       // later calls may run on another stream (ecgpu_set_stream)
+  if (rc || e != hipSuccess) {
+    (void)hipFree(p);
+    return rc ? rc : ecgpu_set_err(c, ECGPU_ERR_RUNTIME, "shared-point table (%d-bit windows): %s", wb, hipGetErrorString(e));
+  }
+  ecgpu_ctx::SharedTable t{p, bytes, curve, wb, clock, {0}};
+  memcpy(t.key, key, kb);
+  c->shared_tabs.push_back(t);
+  c->shared_bytes += bytes;
+  c->opt[ECGPU_OPT_SHARED_TABLE_BUILDS]++;
+  *table = p;
+  return 0;
+}
+}  // namespace shared
+
+// key_mode: `points` is the one key of ecgpu_ecdsa_verify_batch - plan.rep is always filled (the prep kernel reads a key per element), and a
+// key that does not validate is plan.valid = false, not an error.
+static int shared_prepare(ecgpu_ctx* c, const ecgpu_curve_ops* ops, int curve, const uint8_t* points, size_t terms, size_t n, unsigned flags, bool key_mode,
+                          shared::Plan& plan) {
+  const size_t kb = 2 * ecgpu_field_bytes(curve);
+  const bool secret = (flags & ECGPU_SECRET_SCALARS) && !(flags & ECGPU_EXACT_REFERENCE);
+  bool can_table = !(flags & ECGPU_EXACT_REFERENCE) && terms <= (size_t)ECGPU_SHARED_MAX_TERMS;
+  if (can_table && (secret || key_mode) && (terms > 1 || shared::is_identity(points, kb))) can_table = false;
+  const uint64_t clock = ++c->shared_clock;
+  // a budget that was lowered since the tables were built holds from the next call on
+  while (c->shared_bytes > (size_t)c->opt[ECGPU_OPT_SHARED_TABLE_BUDGET]) {
+    const int rc = shared::evict_one(c, -1, clock);
+    if (rc == shared::NOMEM) break;
+    if (rc) return rc;
+  }
+  const size_t min_n = c->opt[ECGPU_OPT_SHARED_MIN] ? (size_t)c->opt[ECGPU_OPT_SHARED_MIN] : shared::default_min(curve);
+  const int pinned = (int)c->opt[ECGPU_OPT_SHARED_WINDOW];
+  const int rule = shared::rule_width(curve, n);
+  const int build_wb = secret ? shared::CT_WB : pinned ? pinned : rule;
+  // the widths a cached table may have to count as a hit: the one a build would pick, a wider one, or - for a batch too small to build - any
+  int cand[4], ncand = 0;
+  cand[ncand++] = build_wb;
+  if (!secret && !pinned)
+    for (int w : {20, 16, 8})
+      if (w != rule && (w > rule || n < min_n)) cand[ncand++] = w;
+  bool hit = false;
+  for (int k = 0; can_table && !hit && k < ncand; k++) {
+    hit = true;
+    for (size_t t = 0; t < terms && hit; t++)
+      hit = shared::is_identity(points + t * kb, kb) || shared::find(c, curve, points + t * kb, kb, cand[k]);
+    if (!hit) continue;
+    plan.wb = cand[k];
+    for (size_t t = 0; t < terms; t++) {
+      ecgpu_ctx::SharedTable* e = shared::is_identity(points + t * kb, kb) ? nullptr : shared::find(c, curve, points + t * kb, kb, cand[k]);
+      if (e) e->used = clock;
+      plan.tabs[t] = e ? e->p : nullptr;
+    }
+  }
+  plan.table = hit;
+  if (hit && !key_mode) return 0;                  // no copy, no synchronisation
+  const bool build = can_table && !hit && n >= min_n;
+  const bool replicate = key_mode || (!hit && !build);
+  uint32_t* xy;
+  uint8_t* okf;
+  void* bases;
+  int rc = ecgpu_carve(c, c->shared_ws, [&](WsCarver& ws) {
+    xy = ws.take<uint32_t>(terms * kb);
+    okf = ws.take<uint8_t>(terms);
+    bases = ws.take<void>(128 * 96);               // one entry per window: at most 77 (P-384, 5-bit windows) of 96 bytes
+    plan.rep = replicate ? ws.take<uint32_t>(n * terms * kb) : nullptr;
+  });
+  if (rc) return rc;
+  const uint32_t* src = xy;
+  if (hit) {
+    src = shared::words_of(*shared::find(c, curve, points, kb, plan.wb));      // key mode: the key's words are behind its table
+  } else {
+    std::vector<uint8_t> ok(terms);
+    HIPCHK(c, hipMemcpyAsync(xy, points, terms * kb, hipMemcpyHostToDevice, c->stream));
+    if ((rc = ops->validate_points(c, xy, okf, terms))) return rc;
+    HIPCHK(c, hipMemcpyAsync(ok.data(), okf, terms, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (size_t t = 0; t < terms; t++) {
+      if (ok[t]) continue;
+      if (!key_mode) return ecgpu_set_err(c, ECGPU_ERR_ARG, "shared point %zu is not a point of the curve (a coordinate not below p, or off the curve)", t);
+      plan.valid = false;
+    }
+  }
+  if (build && plan.valid) {
+    // the width is picked once, before anything is built: all the call's tables (cached ones included: they stay) must fit the budget together
+    int first_wb = build_wb;
+    for (; first_wb != shared::CT_WB && first_wb > 8; first_wb = first_wb == 20 ? 16 : 8) {
+      size_t need = 0;
+      for (size_t t = 0; t < terms; t++) {
+        bool counted = shared::is_identity(points + t * kb, kb);
+        for (size_t u = 0; u < t && !counted; u++) counted = memcmp(points + u * kb, points + t * kb, kb) == 0;
+        if (!counted) need += ops->shared_table_bytes(first_wb);
+      }
+      if (need <= (size_t)c->opt[ECGPU_OPT_SHARED_TABLE_BUDGET]) break;
+    }
+    // (what is left to step down for: hipErrorOutOfMemory, and a curve's 16 tables all in use by this call)
+    for (int wb = first_wb;;) {
+      bool nomem = false;
+      for (size_t t = 0; t < terms && !nomem; t++) {
+        plan.tabs[t] = nullptr;
+        if (shared::is_identity(points + t * kb, kb)) continue;
+        rc = shared::ensure(c, ops, curve, points + t * kb, kb, wb, xy + t * (kb / 4), bases, clock, &plan.tabs[t]);
+        if (rc == shared::NOMEM) nomem = true;
+        else if (rc) return rc;
+      }
+      plan.wb = wb;
+      if (!nomem) break;
+      if (wb == shared::CT_WB || wb == 8)
+        return ecgpu_set_err(c, ECGPU_ERR_RUNTIME, "shared points: the %d-bit tables of this call fit neither ECGPU_OPT_SHARED_TABLE_BUDGET nor the device's memory", wb);
+      wb = wb == 20 ? 16 : 8;
+    }
+    plan.table = true;
+  }
+  if (plan.rep && (rc = ops->broadcast_points(c, src, terms, plan.rep, n))) return rc;
+  return 0;
+}
+
 static int lincomb_impl(ecgpu_ctx* c, int curve, const uint8_t* scalars, const uint8_t* points, int pt_fmt, size_t terms, uint8_t* out, int out_fmt,
                         uint8_t* out_inf, uint8_t* scalar_ok, size_t n, int mem, unsigned flags) {
   if (!c || !scalars || !out) return ecgpu_set_err(c, ECGPU_ERR_ARG, "null argument");
   if ((pt_fmt != ECGPU_PT_AFFINE && pt_fmt != ECGPU_PT_PROJECTIVE) || (out_fmt != ECGPU_PT_AFFINE && out_fmt != ECGPU_PT_PROJECTIVE))
     return ecgpu_set_err(c, ECGPU_ERR_ARG, "bad point format");
   if (terms == 0) return ecgpu_set_err(c, ECGPU_ERR_ARG, "terms must be >= 1");
+  if ((flags & ECGPU_SHARED_POINTS) && (!points || pt_fmt != ECGPU_PT_AFFINE))
+    return ecgpu_set_err(c, ECGPU_ERR_ARG, "ECGPU_SHARED_POINTS takes `terms` affine points in host memory");
   if (n == 0) return ECGPU_OK;
   ENTER(c, curve);
   const size_t pin = (pt_fmt == ECGPU_PT_PROJECTIVE ? 3 : 2) * nb, pout = (out_fmt == ECGPU_PT_PROJECTIVE ? 3 : 2) * nb;
+  if (flags & ECGPU_SHARED_POINTS) {
+    // the points are no per-element buffer: they stay out of the list (the host pipeline must not chunk them) and their tables stand before run_batch
+    const unsigned kflags = flags & ~(unsigned)ECGPU_SHARED_POINTS;
+    if (terms > 1024) return ecgpu_set_err(c, ECGPU_ERR_UNSUPPORTED, "lincomb_batch: at most 1024 terms per combination");
+    shared::Plan plan;
+    int rc = shared_prepare(c, ops, curve, points, terms, n, kflags, false, plan);
+    if (rc) return rc;
+    const unsigned sc_secret = (kflags & (ECGPU_EXACT_REFERENCE | ECGPU_SECRET_SCALARS)) ? ARG_SECRET : 0;
+    const unsigned out_secret = (kflags & ECGPU_SECRET_SCALARS) ? ARG_SECRET : 0;
+    const CallArg args[] = {arg_in(scalars, terms * nb, sc_secret), arg_out(out, pout, out_secret),
+                            arg_out(out_fmt == ECGPU_PT_AFFINE ? out_inf : nullptr, 1, ARG_OPTIONAL), arg_out(scalar_ok, 1, ARG_OPTIONAL)};
+    const size_t pass = plan.table ? ops->pass_units(c, 0, 1, kflags) : ops->pass_units(c, 1, terms, kflags);
+    return run_batch(c, mem, n, args, pass, [&](void** d, size_t cnt) {
+      if (d[3]) {
+        int rc2 = ops->validate_scalars(c, (const uint32_t*)d[0], (uint8_t*)d[3], cnt, terms);
+        if (rc2) return rc2;
+      }
+      if (plan.table) return ops->shared_lincomb(c, (const uint32_t*)d[0], plan.tabs, plan.wb, terms, (uint32_t*)d[1], out_fmt, (uint8_t*)d[2], cnt, kflags);
+      // every chunk reads the replicated points from their start: the rows repeat with period `terms`
+      return ops->lincomb(c, (const uint32_t*)d[0], plan.rep, ECGPU_PT_AFFINE, terms, (uint32_t*)d[1], out_fmt, (uint8_t*)d[2], cnt, kflags);
+    });
+  }
   // the reference schedule is the one meant for secret scalars: their staged copies do not outlive the call; for a secret scalar
   // the product is a secret too
   const unsigned sc_secret = (flags & (ECGPU_EXACT_REFERENCE | ECGPU_SECRET_SCALARS)) ? ARG_SECRET : 0;
@@ -644,6 +874,21 @@ int ecgpu_ecdsa_verify_batch(ecgpu_ctx* c, int curve, const uint8_t* prehash, co
   if (!c || !prehash || !sig_rs || !pubkeys_xy || !ok) return ecgpu_set_err(c, ECGPU_ERR_ARG, "null argument");
   if (n == 0) return ECGPU_OK;
   ENTER(c, curve);
+  if (flags & ECGPU_SHARED_POINTS) {
+    // one key in host memory for the whole batch: it leaves the list, the prep kernel reads its replicated copy (the same rows for every
+    // chunk), u2 Q runs on the key's table.  A key the per-element call would reject - invalid, or the identity - and a batch too small
+    // to build a table for go through the per-element launcher on the copy: ok = 0 throughout for the former.
+    const unsigned kflags = flags & ~(unsigned)ECGPU_SHARED_POINTS;
+    shared::Plan plan;
+    int rc = shared_prepare(c, ops, curve, pubkeys_xy, 1, n, 0, true, plan);
+    if (rc) return rc;
+    const CallArg args[] = {arg_in(prehash, nb), arg_in(sig_rs, 2 * nb), arg_out(ok, 1)};
+    return run_batch(c, mem, n, args, ops->pass_units(c, plan.table ? 0 : 1, 1, 0), [&](void** d, size_t cnt) {
+      if (plan.table)
+        return ops->ecdsa_verify_shared(c, (const uint32_t*)d[0], (const uint32_t*)d[1], plan.rep, plan.tabs[0], plan.wb, (uint8_t*)d[2], cnt, kflags);
+      return ops->ecdsa_verify(c, (const uint32_t*)d[0], (const uint32_t*)d[1], plan.rep, (uint8_t*)d[2], cnt, kflags);
+    });
+  }
   const CallArg args[] = {arg_in(prehash, nb), arg_in(sig_rs, 2 * nb), arg_in(pubkeys_xy, 2 * nb), arg_out(ok, 1)};
   return run_batch(c, mem, n, args, ops->pass_units(c, 1, 1, 0), [&](void** d, size_t cnt) {
     return ops->ecdsa_verify(c, (const uint32_t*)d[0], (const uint32_t*)d[1], (const uint32_t*)d[2], (uint8_t*)d[3], cnt, flags);
@@ -932,6 +1177,7 @@ static int sign_from_msgs(ecgpu_ctx* c, const char* what, int curve, int hash, c
 static int verify_from_msgs(ecgpu_ctx* c, const char* what, int curve, int hash, const uint8_t* msgs, size_t msg_stride, const uint32_t* msg_len, const uint8_t* sig_rs,
                             const uint8_t* pubkeys_xy, uint8_t* ok, size_t n, int mem, unsigned flags) {
   if (!c || !sig_rs || !pubkeys_xy || !ok) return ecgpu_set_err(c, ECGPU_ERR_ARG, "null argument");
+  if (flags & ECGPU_SHARED_POINTS) return ecgpu_set_err(c, ECGPU_ERR_UNSUPPORTED, "%s takes one key per element: ECGPU_SHARED_POINTS is for ecgpu_ecdsa_verify_batch", what);
   int rc = hash_fits(c, what, curve, hash);
   if (rc) return rc;
   if ((rc = msgs_enter(c, msgs, msg_stride, msg_len, n, mem))) return rc;

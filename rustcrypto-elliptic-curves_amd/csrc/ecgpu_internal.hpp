@@ -7,6 +7,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <mutex>
+#include <vector>
 
 #include "../../include/ecgpu.h"
 #include "ws_carver.hpp"
@@ -29,6 +30,9 @@ enum ecgpu_table_kind {
   ECGPU_TAB_COUNT_
 };
 
+// terms of one shared-points call that can run from tables (fb::SHARED_MAX_TERMS, sharedbase.hpp: curve_ops.hpp asserts they agree)
+constexpr int ECGPU_SHARED_MAX_TERMS = 8;
+
 struct ecgpu_ctx {
   int device = -1;
   int num_cus = 0;
@@ -39,7 +43,7 @@ struct ecgpu_ctx {
   char err[512] = {0};
   std::mutex mu;
   std::mutex err_mu;                          // guards err[] (ecgpu_set_err / ecgpu_last_error_copy)
-  int64_t opt[ECGPU_OPT_COUNT_] = {0, 26, 0, 0, 1, 0, 4, 0, 0};      // ecgpu_option defaults
+  int64_t opt[ECGPU_OPT_COUNT_] = {0, 26, 0, 0, 1, 0, 4, 0, 0, 0, 0, (int64_t)1 << 31, 0};      // ecgpu_option defaults
   // grow-only device staging buffers for ECGPU_MEM_HOST calls: 6 for whole-batch staging, then PIPE_NSLOT pipeline slots x PIPE_ARGS0 arguments.
   // The message-level signing calls have a seventh buffer (four inputs): its slots follow behind, so that every older slot keeps its
   // number - STAGE_IN3 for a whole batch, then one per pipeline slot (hostpipe::stage_index).
@@ -61,6 +65,22 @@ struct ecgpu_ctx {
   void* table[ECGPU_TAB_COUNT_][3] = {};             // [kind][curve]
   size_t fb_bytes[3] = {0, 0, 0};                      // device memory held by the generator tables of a curve
   int fb_widest[3] = {0, 0, 0};
+  // Tables of shared points (ECGPU_SHARED_POINTS; ecgpu.hip, shared points): keyed by curve, the point's affine bytes and the window
+  // width, at most SHARED_TABLES_PER_CURVE per curve and ECGPU_OPT_SHARED_TABLE_BUDGET bytes over all, least recently used out first.
+  // An allocation holds the table and, behind it, the point's canonical x || y words (what a shared key's prep kernel reads).
+  struct SharedTable {
+    void* p;
+    size_t bytes;              // of the table itself; the point's words follow
+    int curve, wb;
+    uint64_t used;             // shared_clock at the last call that used it
+    uint8_t key[96];           // x || y, 2 NB bytes
+  };
+  static constexpr size_t SHARED_TABLES_PER_CURVE = 16;
+  std::vector<SharedTable> shared_tabs;
+  uint64_t shared_clock = 0;
+  size_t shared_bytes = 0;
+  // the call's points on the device, their validation flags, the builders' window bases and the broadcast path's replicated points
+  DevBuf shared_ws;
   // Workspaces (grow-only; DESIGN section 1, Workspaces).  The rule: the OUTERMOST launcher of a call carves a buffer, once
   // (ecgpu_carve below); whatever it calls receives pointers and never carves that buffer again - growing loses the contents.
   // per-lane tables of the variable-base, Straus and reference kernels: one buffer used whole, reserved by the launcher of that kernel
@@ -212,6 +232,19 @@ struct ecgpu_curve_ops {
   // element valid.  ok (NULL allowed with ECGPU_BATCH_VERDICT_ONLY) as include/ecgpu.h describes.
   int (*schnorr_batch_verify)(ecgpu_ctx* c, const uint32_t* px, const uint32_t* sig, const uint32_t* e, uint8_t* ok, size_t n, uint64_t first_index,
                               const uint8_t* seed32, unsigned flags, int* verdict);
+  // shared points (sharedbase.hpp; the cache of the tables is the API layer's, ecgpu.hip).  shared_table_bytes: size of a table of
+  // window width wb (5 | 8 | 16 | 20), 0 for any other width; shared_build: enqueues the two builder stages for the point at xy (device
+  // memory, canonical words; `bases` is scratch for one entry per window); shared_lincomb: out[i] = sum_t sc[i terms + t] H_t from
+  // `terms` <= 8 tables of width wb (a null table: the identity; ECGPU_SECRET_SCALARS: one table of width 5 on the constant-time
+  // kernel); broadcast_points: dst = the `terms` points at xy repeated n times; ecdsa_verify_shared: ecdsa_verify whose u2 Q runs on
+  // Q's table, q_rep holding Q repeated n times for the prep kernel
+  size_t (*shared_table_bytes)(int wb);
+  int (*shared_build)(ecgpu_ctx* c, const uint32_t* xy, int wb, void* bases, void* table);
+  int (*shared_lincomb)(ecgpu_ctx* c, const uint32_t* sc, const void* const* tables, int wb, size_t terms, uint32_t* out, int out_fmt, uint8_t* out_inf,
+                        size_t n, unsigned flags);
+  int (*broadcast_points)(ecgpu_ctx* c, const uint32_t* xy, size_t terms, uint32_t* dst, size_t n);
+  int (*ecdsa_verify_shared)(ecgpu_ctx* c, const uint32_t* z, const uint32_t* sig, const uint32_t* q_rep, const void* table, int wb, uint8_t* ok, size_t n,
+                             unsigned flags);
 };
 // Signatures from which ecgpu_schnorr_batch_verify* takes the equation by default.  Under the MSM's small-sum limit (2n + 1 below
 // msm_kernels.hpp SMALL_MSM_TERMS; msm_k256.hip asserts the relation) the MSM is itself one multiplication per term and the equation

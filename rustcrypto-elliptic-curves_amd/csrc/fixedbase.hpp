@@ -13,6 +13,7 @@
 #pragma once
 #include "jacobian.hpp"
 #include "fixedbase_ct.hpp"
+#include "sharedbase.hpp"
 #include "kernels.hpp"
 #include "sched.hpp"
 #include "msm.hpp"                // XYZZ accumulators (8M + 2S per mixed addition)
@@ -31,11 +32,7 @@ template <class C> constexpr int nwin() { return C::NB + 1; }            // one 
 //   (ECGPU_FB_MAX_WINDOW caps the width a context will build, ECGPU_FB_WINDOW pins it)
 //   (p256, 2^24 results: 16.1 / 14.2 / 13.3 ms with WB = 20 / 24 / 26 - every addition a window saves is 11 of ~140
 //   multiplications, and the gathers from a table no cache holds stay hidden behind them)
-// When WB divides the scalar width the signed recoding can carry out of the top window (one extra window that only
-// ever sees digit 1); otherwise the top window has spare bits and absorbs the carry.
-template <int WB> constexpr int wide_entries() { return 1 << (WB - 1); }
-template <class C, int WB> constexpr bool wide_carry_window() { return (8 * C::NB) % WB == 0; }
-template <class C, int WB> constexpr int nwin_wide() { return (8 * C::NB + WB - 1) / WB + (wide_carry_window<C, WB>() ? 1 : 0); }
+// (wide_entries, wide_carry_window and nwin_wide, the geometry of these tables, are in fixedbase_ct.hpp: the host twin reads them too)
 
 // stage A: one lane per window computes d * 2^(8j) G, d = 1..128, in Jacobian coordinates
 template <class C>
@@ -442,6 +439,77 @@ __global__ void __launch_bounds__(256, WAVES) mul_ct_kernel(const u32* scalars, 
       }
       if (out_inf) out_inf[i] = inf ? 1 : 0;
     }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Shared points (sharedbase.hpp): the builders of a table for a point that is not G, the broadcast of the fallback path and
+// the multi-table kernel.
+// ---------------------------------------------------------------------------------------------------------------------
+// stage A: lane j writes B_j = 2^(WB j) H; xy = H, canonical x || y words
+template <class C, int WB>
+__global__ void __launch_bounds__(64) shared_bases_kernel(const u32* xy, AffEntry<C>* bases) {
+  const int j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= nwin_wide<C, WB>()) return;
+  AffEntry<C> h, b;
+  C::fe_load(h.x, xy);
+  C::fe_load(h.y, xy + C::NW);
+  shared_window_base<C>(b, h, WB * j);
+  bases[j] = b;
+}
+// stage B: one lane per run of SHARED_RUN entries, written with 16-byte stores (an entry is 64 or 96 bytes, the table 16-byte aligned)
+template <class C, int WB>
+__global__ void __launch_bounds__(256) shared_runs_kernel(const AffEntry<C>* bases, AffEntry<C>* table, size_t runs) {
+  constexpr size_t RUNS_PER_WINDOW = wide_entries<WB>() / SHARED_RUN;
+  static_assert(wide_entries<WB>() % SHARED_RUN == 0 && sizeof(AffEntry<C>) % 16 == 0, "whole runs per window, whole 16-byte pieces per entry");
+  ECGPU_GRID_STRIDE(r, runs) {
+    const size_t j = r / RUNS_PER_WINDOW, q = r % RUNS_PER_WINDOW;
+    alignas(16) AffEntry<C> ent[SHARED_RUN];
+    shared_run<C>(ent, bases[j], (u32)(q * SHARED_RUN) + 1u);
+    const uint4* src = reinterpret_cast<const uint4*>(ent);
+    uint4* dst = reinterpret_cast<uint4*>(table + j * wide_entries<WB>() + q * SHARED_RUN);
+#pragma unroll 4
+    for (int w = 0; w < (int)(SHARED_RUN * sizeof(AffEntry<C>) / 16); w++) dst[w] = src[w];
+  }
+}
+// the broadcast path: dst = the row of row_words words (the call's `terms` points) repeated `rows` times
+template <class C>
+__global__ void __launch_bounds__(256) broadcast_points_kernel(const u32* row, size_t row_words, u32* dst, size_t rows) {
+  ECGPU_GRID_STRIDE(w, rows * row_words) dst[w] = row[w % row_words];
+}
+
+// out[i] = sum_t scalars[i terms + t] H_t, 2 .. SHARED_MAX_TERMS tables (one table: mul_kernel / mul_wide_kernel above, unchanged):
+// the work distribution and the result buffer of mul_wide_kernel around mul_shared_one.  Always dynamically scheduled.
+template <class C, int WB, int BATCH, int WAVES>
+__global__ void __launch_bounds__(256, WAVES) mul_shared_kernel(const u32* scalars, SharedTabs<C> tabs, u32* out, int out_fmt, uint8_t* out_inf,
+                                                             size_t n_all, WaveSched sched) {
+  constexpr int NW = C::NW;
+  typename FbAcc<C>::Pt res[BATCH];
+  typename C::Fe pre[BATCH];
+  size_t idx[BATCH];                 // global index of every buffered result
+  int cnt = 0, slots = 0;            // results buffered by this lane; per-lane units drawn since the last flush (wave-uniform)
+  for (;;) {
+    size_t lo, n = n_all;
+    const bool more = wave_next_chunk(sched, lo, n);
+    const size_t base = lo + (threadIdx.x & 63u);
+    const int units = more ? (int)((n - lo + 63) / 64) : 0;
+#pragma unroll 1
+    for (int b = 0; b < units; b++) {
+      const size_t i = base + (size_t)b * 64;
+      if (i >= n) break;
+      typename FbAcc<C>::Pt acc;
+      mul_shared_one<C, WB, FbAcc<C>>(acc, scalars + i * (size_t)tabs.terms * NW, tabs);
+      res[cnt] = acc;
+      idx[cnt] = i;
+      cnt++;
+    }
+    slots += units;
+    if (!more || slots + (int)sched.chunk_units > BATCH) {
+      if (cnt) FbAcc<C>::store(res, pre, cnt, 0, 0, out, out_fmt, out_inf, idx);
+      cnt = 0;
+      slots = 0;
+    }
+    if (!more) break;
   }
 }
 

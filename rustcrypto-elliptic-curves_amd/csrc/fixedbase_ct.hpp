@@ -11,6 +11,12 @@ namespace fb {
 constexpr int CT_WB = 5;                                        // signed 5-bit digits
 constexpr int CT_ENTRIES = 1 << (CT_WB - 1);                    // T[j][d-1] = d 2^(5j) G, d = 1..16
 template <class C> constexpr int ct_nwin() { return (8 * C::NB + CT_WB - 1) / CT_WB; }
+// Geometry of every digit-indexed table T[j][d-1] = d 2^(WB j) B (the generator's, fixedbase.hpp, and a shared point's,
+// sharedbase.hpp): 2^(WB-1) entries per window.  When WB divides the scalar width the signed recoding can carry out of the top
+// window (one extra window that only ever sees digit 1); otherwise the top window has spare bits and absorbs the carry.
+template <int WB> constexpr int wide_entries() { return 1 << (WB - 1); }
+template <class C, int WB> constexpr bool wide_carry_window() { return (8 * C::NB) % WB == 0; }
+template <class C, int WB> constexpr int nwin_wide() { return (8 * C::NB + WB - 1) / WB + (wide_carry_window<C, WB>() ? 1 : 0); }
 
 // p += (x2, y2) in XYZZ coordinates (madd-2008-s, 8M + 2S), NO exceptional-case handling: valid iff p is finite and
 // p != +-(x2, y2); anything else gives garbage that the caller masks away.
@@ -76,6 +82,10 @@ ECGPU_HD void xyzz_ct_accumulate(msm::Xyzz<C>& acc, u32& empty, const typename C
 //             2^255 (1 - 2^-32) for P-256, 2^380 (1 - 2^-252) for P-384 - all above the 0.52 * 32^j that bounds |S_j|
 //             (tests/test_oracle_golden.py::test_fixed_base_ct_top_window checks the three moduli).
 // So the only special operands are the empty accumulator and a zero digit, both masks.
+// Nothing above uses a property of G but its order: the accumulator is S_j B for whatever base B the table was built from, and
+// "n | S" is "S B = O" for every B of order n - every point of these cofactor-1 curves but the identity.  So the argument holds
+// unchanged for the 5-bit table of a shared point (sharedbase.hpp builds it, ECGPU_SECRET_SCALARS | ECGPU_SHARED_POINTS runs this
+// body on it); the identity has no table and never comes here.
 template <class C>
 ECGPU_HD void mul_ct_one(typename C::Pt& out, const u32* k, const AffEntry<C>* table) {
   constexpr int NW = C::NW, NWIN = ct_nwin<C>();

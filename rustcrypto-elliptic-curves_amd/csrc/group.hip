@@ -188,6 +188,8 @@ int ecgpu_group_lincomb_batch(ecgpu_group* g, int curve, const uint8_t* scalars,
   const size_t nb = ecgpu_field_bytes(curve);
   if (!nb) return group_err(g, ECGPU_ERR_UNSUPPORTED, "curve %d not supported", curve);
   if (!scalars || !out || terms == 0) return group_err(g, ECGPU_ERR_ARG, "null argument or zero terms");
+  // the members' ranges are cut out of per-element buffers: a shared point's short buffer would be read as n points
+  if (flags & ECGPU_SHARED_POINTS) return group_err(g, ECGPU_ERR_UNSUPPORTED, "the group forms take per-element points: ECGPU_SHARED_POINTS is for the single-context calls");
   std::lock_guard<std::mutex> lk(g->mu);
   const int k = (int)g->ctx.size();
   const size_t pin = (pt_fmt == ECGPU_PT_PROJECTIVE ? 3 : 2) * nb, pout = (out_fmt == ECGPU_PT_PROJECTIVE ? 3 : 2) * nb;
@@ -210,6 +212,7 @@ int ecgpu_group_lincomb_sharded(ecgpu_group* g, int curve, const uint8_t* const*
                                 uint8_t* const* out, int out_fmt, uint8_t* const* out_inf, const size_t* counts, unsigned flags) {
   if (!g) return ECGPU_ERR_ARG;
   if (!scalars || !out || !counts || terms == 0) return group_err(g, ECGPU_ERR_ARG, "null argument or zero terms");
+  if (flags & ECGPU_SHARED_POINTS) return group_err(g, ECGPU_ERR_UNSUPPORTED, "the group forms take per-element points: ECGPU_SHARED_POINTS is for the single-context calls");
   std::lock_guard<std::mutex> lk(g->mu);
   std::vector<int> rc;
   const int bad = for_each_member(g, rc, [&](int i) {

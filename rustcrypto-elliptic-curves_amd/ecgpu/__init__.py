@@ -34,6 +34,7 @@ ECDSA_LOW_S = 2
 PUBLIC_SCALARS = 4
 SECRET_SCALARS = 8
 BATCH_VERDICT_ONLY, BATCH_EQUATION_ALWAYS = 16, 32                     # ecgpu_schnorr_batch_verify*
+SHARED_POINTS = 64                                                     # mul / lincomb / ecdsa_verify: `terms` host points (one key) for the whole batch
 K256, P256, P384 = 0, 1, 2
 CURVE_IDS = {"k256": K256, "p256": P256, "p384": P384}
 FIELD_BYTES = {K256: 32, P256: 32, P384: 48}
@@ -48,7 +49,8 @@ CURVE_HASH = {K256: SHA256, P256: SHA256, P384: SHA384}                # the has
 OKM_BYTES = {K256: 48, P256: 48, P384: 72}                             # FromOkm::Length
 DIGEST_BYTES = {SHA256: 32, SHA384: 48, KECCAK256: 32, SHA3_256: 32, SHA3_384: 48}
 # ecgpu_option (per-context tuning / test knobs, include/ecgpu.h)
-OPT_FB_WINDOW, OPT_FB_MAX_WINDOW, OPT_MSM_WINDOW_BITS, OPT_MSM_SLAB_TERMS, OPT_MSM_SMALL_PATH, OPT_MSM_ROUNDS, OPT_K256_WAVES, OPT_FB_MEMORY_BUDGET, OPT_LINCOMB_TERM_BY_TERM = range(9)
+(OPT_FB_WINDOW, OPT_FB_MAX_WINDOW, OPT_MSM_WINDOW_BITS, OPT_MSM_SLAB_TERMS, OPT_MSM_SMALL_PATH, OPT_MSM_ROUNDS, OPT_K256_WAVES, OPT_FB_MEMORY_BUDGET,
+ OPT_LINCOMB_TERM_BY_TERM, OPT_SHARED_WINDOW, OPT_SHARED_MIN, OPT_SHARED_TABLE_BUDGET, OPT_SHARED_TABLE_BUILDS) = range(13)
 
 _PKG_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # ECGPU_LIB: another build of the library (A/B measurements of compile-time switches); default: the in-tree build
@@ -505,14 +507,18 @@ class Curve:
     def lincomb(self, scalars, points, terms: int = 1, point_format: int = AFFINE, out_format: int = AFFINE, flags: int = 0,
                 out=None, out_inf=None, checked: bool = False):
         """out / out_inf: optional preallocated result arrays (e.g. Context.pinned_array) instead of fresh ones.
-        checked=True also returns scalar_ok (Scalar::from_repr: 0 where a scalar of the element is >= n)."""
+        checked=True also returns scalar_ok (Scalar::from_repr: 0 where a scalar of the element is >= n).
+        flags & SHARED_POINTS: `points` holds exactly `terms` affine points that every element uses (include/ecgpu.h)."""
         s = _as_host(scalars, self.nb)
         if terms < 1 or len(s) % terms:
             raise ValueError("the number of scalars is not a multiple of `terms`")
         n = len(s) // terms
         ow = _point_bytes(out_format, self.nb)
         p = _as_host(points, _point_bytes(point_format, self.nb)) if points is not None else None
-        if p is not None and len(p) != n * terms:
+        if flags & SHARED_POINTS:
+            if p is None or point_format != AFFINE or len(p) != terms:
+                raise ValueError("SHARED_POINTS takes exactly `terms` affine points (%d terms, %s points)" % (terms, "no" if p is None else len(p)))
+        elif p is not None and len(p) != n * terms:
             raise ValueError("scalars and points differ in count (%d scalars, %d points)" % (len(s), len(p)))
         out = _host_out(n, ow) if out is None else out
         inf = _host_flags(n) if out_inf is None else out_inf
@@ -564,8 +570,14 @@ class Curve:
 
     def mul_device(self, d_scalars, d_points, d_out, n: int, point_format: int = AFFINE, out_format: int = AFFINE,
                    d_out_inf=None, flags: int = 0):
+        """flags & SHARED_POINTS: d_points is ONE affine point in HOST memory (bytes or a numpy array), whatever its name says."""
         self._check_device(d_scalars, n * self.nb, "d_scalars")
-        self._check_device(d_points, n * _point_bytes(point_format, self.nb), "d_points")
+        if flags & SHARED_POINTS:
+            d_points = _as_host(d_points, 2 * self.nb)
+            if point_format != AFFINE or len(d_points) != 1:
+                raise ValueError("SHARED_POINTS takes exactly one affine point in host memory")
+        else:
+            self._check_device(d_points, n * _point_bytes(point_format, self.nb), "d_points")
         self._check_device(d_out, n * _point_bytes(out_format, self.nb), "d_out")
         self._check_device(d_out_inf, n, "d_out_inf")
         self._call("ecgpu_mul_batch", d_scalars, d_points, point_format, d_out, out_format, d_out_inf, n, DEVICE, flags)
@@ -638,13 +650,24 @@ class Curve:
         return ECDSA_LOW_S if self.id == K256 else 0
 
     def ecdsa_verify(self, prehash, sig_rs, pubkeys_xy, flags: Optional[int] = None) -> np.ndarray:
+        """flags & SHARED_POINTS: pubkeys_xy is ONE key that every signature is checked against."""
         z, sg, q = _as_host(prehash, self.nb), _as_host(sig_rs, 2 * self.nb), _as_host(pubkeys_xy, 2 * self.nb)
-        _equal_lengths("prehash, signature and public-key", z, sg, q)
+        if self._flags(flags) & SHARED_POINTS:
+            if len(q) != 1:
+                raise ValueError("SHARED_POINTS takes exactly one public key (%d given)" % len(q))
+            _equal_lengths("prehash and signature", z, sg)
+        else:
+            _equal_lengths("prehash, signature and public-key", z, sg, q)
         ok = _host_flags(len(z))
         self._call("ecgpu_ecdsa_verify_batch", z, sg, q, ok, len(z), HOST, self._flags(flags))
         return ok
 
     def ecdsa_verify_device(self, d_prehash, d_sig_rs, d_pubkeys_xy, d_ok, n: int, flags: Optional[int] = None):
+        """flags & SHARED_POINTS: d_pubkeys_xy is ONE key in HOST memory (bytes or a numpy array), whatever its name says."""
+        if self._flags(flags) & SHARED_POINTS:
+            d_pubkeys_xy = _as_host(d_pubkeys_xy, 2 * self.nb)
+            if len(d_pubkeys_xy) != 1:
+                raise ValueError("SHARED_POINTS takes exactly one public key in host memory (%d given)" % len(d_pubkeys_xy))
         self._call("ecgpu_ecdsa_verify_batch", d_prehash, d_sig_rs, d_pubkeys_xy, d_ok, n, DEVICE, self._flags(flags))
 
     def map_to_curve(self, u, count: int = 1):
@@ -965,6 +988,8 @@ class Group:
         _call(self, "ecgpu_group_synchronize")
 
     def lincomb(self, curve, scalars, points, terms: int = 1, point_format: int = AFFINE, out_format: int = AFFINE, flags: int = 0, out=None, out_inf=None):
+        if flags & SHARED_POINTS:
+            raise ValueError("SHARED_POINTS is for the single-context calls: the group forms take per-element points")
         cid = _curve_id(curve)
         nb = FIELD_BYTES[cid]
         s = _as_host(scalars, nb)

@@ -68,6 +68,9 @@ pub const ECGPU_SECRET_SCALARS: c_uint = 8;
 /// flags of `ecgpu_schnorr_batch_verify*`: no per-signature fallback / the equation at every batch size
 pub const ECGPU_BATCH_VERDICT_ONLY: c_uint = 16;
 pub const ECGPU_BATCH_EQUATION_ALWAYS: c_uint = 32;
+/// `points` (mul / lincomb) holds `terms` points, `pubkeys_xy` (`ecgpu_ecdsa_verify_batch`) one key, in HOST memory, that every
+/// element uses: multiplied from a table cached in the context; results as with the points replicated
+pub const ECGPU_SHARED_POINTS: c_uint = 64;
 /// `ecgpu_option`: per-context tuning / test knobs (the library never reads the process environment)
 pub const ECGPU_OPT_FB_WINDOW: c_int = 0;
 pub const ECGPU_OPT_FB_MAX_WINDOW: c_int = 1;
@@ -78,7 +81,11 @@ pub const ECGPU_OPT_MSM_ROUNDS: c_int = 5;
 pub const ECGPU_OPT_K256_WAVES: c_int = 6;
 pub const ECGPU_OPT_FB_MEMORY_BUDGET: c_int = 7;
 pub const ECGPU_OPT_LINCOMB_TERM_BY_TERM: c_int = 8;
-pub const ECGPU_OPT_COUNT_: c_int = 9;
+pub const ECGPU_OPT_SHARED_WINDOW: c_int = 9;
+pub const ECGPU_OPT_SHARED_MIN: c_int = 10;
+pub const ECGPU_OPT_SHARED_TABLE_BUDGET: c_int = 11;
+pub const ECGPU_OPT_SHARED_TABLE_BUILDS: c_int = 12;
+pub const ECGPU_OPT_COUNT_: c_int = 13;
 /// `ecgpu_group_create` flag: gather the partial sums of a split sum through host memory even where RCCL could be used
 pub const ECGPU_GROUP_NO_RCCL: c_uint = 1;
 
