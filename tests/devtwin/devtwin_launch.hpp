@@ -1,5 +1,5 @@
-// TEST-ONLY host-side plumbing shared by the launchers of devtwin_group.hip and devtwin_rfc6979.hip: device copies of host word
-// arrays that free themselves, and the first-error return of an entry point.
+// TEST-ONLY host-side plumbing shared by the launchers of devtwin_group.hip, devtwin_rfc6979.hip and devtwin_ecdsa.hip: device
+// copies of host word arrays that free themselves, and the first-error return of an entry point.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -10,7 +10,7 @@ namespace twin {
 
 // device copies of up to MAXN host arrays; the destructor frees whatever was allocated
 struct DevArrays {
-  static constexpr int MAXN = 6;
+  static constexpr int MAXN = 8;
   void* p[MAXN] = {};
   int count = 0;
   ~DevArrays() {
@@ -33,6 +33,20 @@ struct DevArrays {
     p[count++] = q;
     d = static_cast<u32*>(q);
     return hipMemset(q, 0, words * sizeof(u32));
+  }
+  // the same for byte arrays (flags, one per row), held in whole words on the device
+  hipError_t in_bytes(const uint8_t*& d, const uint8_t* h, size_t bytes) {
+    u32* q = nullptr;
+    hipError_t err = outbuf(q, (bytes + 3) / 4);
+    if (err != hipSuccess) return err;
+    d = reinterpret_cast<const uint8_t*>(q);
+    return hipMemcpy(q, h, bytes, hipMemcpyHostToDevice);
+  }
+  hipError_t outbuf_bytes(uint8_t*& d, size_t bytes) {
+    u32* q = nullptr;
+    hipError_t err = outbuf(q, (bytes + 3) / 4);
+    d = reinterpret_cast<uint8_t*>(q);
+    return err;
   }
 };
 

@@ -1,5 +1,5 @@
-"""Loader for the test-only gfx950 builds of the field and scalar primitives, the point formulas and the RFC 6979 generator
-(tests/devtwin) and their host counterpart (tests/hosttwin, the same op tables).  Arrays are (n, words) little-endian uint32; every call checks the return code and
+"""Loader for the test-only gfx950 builds of the field and scalar primitives, the point formulas, the RFC 6979 generator and
+the ECDSA sign_finish / verify_check kernels (tests/devtwin) and their host counterpart (tests/hosttwin, the same op tables).  Arrays are (n, words) little-endian uint32; every call checks the return code and
 raises at the first non-zero one."""
 import ctypes
 import os
@@ -11,7 +11,9 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 DEVTWIN = os.path.join(HERE, "devtwin")
 BUILDS = {"default": "libecdevtwin.so", "bf": "libecdevtwin_bf.so", "grouped": "libecdevtwin_grouped.so",
           # the point formulas (devtwin_group.hip) in the two configurations that ship them, and the RFC 6979 generator
-          "group": "libecdevtwin_group.so", "group_bf": "libecdevtwin_group_bf.so", "rfc6979": "libecdevtwin_rfc6979.so"}
+          "group": "libecdevtwin_group.so", "group_bf": "libecdevtwin_group_bf.so", "rfc6979": "libecdevtwin_rfc6979.so",
+          # ecdsa::sign_finish_kernel and ecdsa::verify_check_kernel on chosen R, A and B
+          "ecdsa": "libecdevtwin_ecdsa.so"}
 _LIBS = {}
 
 # op tables of tests/devtwin/primitive_ops.hpp
@@ -129,3 +131,38 @@ def rfc6979_generate_k(hash_id, xs, h1s, extras, q):
            "rfc6979 generate_k")
     raw = np.ascontiguousarray(k, dtype="<u4").tobytes()
     return [int.from_bytes(raw[4 * nw * i:4 * nw * (i + 1)], "little") for i in range(n)], [int(r) for r in rej]
+
+
+# the ECDSA kernels (tests/devtwin/devtwin_ecdsa.hip): rows of big-endian bytes, as on the C ABI
+def _byte_rows(rows, width):
+    a = np.frombuffer(b"".join(rows), dtype=np.uint8).reshape(len(rows), width).copy()
+    assert a.ctypes.data % 4 == 0
+    return a
+
+
+def _bp(a):
+    return a.ctypes.data_as(ctypes.c_void_p)
+
+
+def ecdsa_sign_finish(curve, d, k, z, r_xy, r_inf, flags):
+    """dt_ecdsa_sign_finish over lists of byte strings (d, k, z: one scalar long; r_xy: x || y of R) and a list of identity flags
+    -> (sig (n, 2 nb), recid (n,), ok (n,)), uint8"""
+    nb = 48 if curve == "p384" else 32
+    n = len(d)
+    assert len(k) == len(z) == len(r_xy) == len(r_inf) == n
+    cols = [_byte_rows(d, nb), _byte_rows(k, nb), _byte_rows(z, nb), _byte_rows(r_xy, 2 * nb), np.array(r_inf, dtype=np.uint8)]
+    sig, recid, ok = np.zeros((n, 2 * nb), dtype=np.uint8), np.full(n, 0xEE, dtype=np.uint8), np.full(n, 0xEE, dtype=np.uint8)
+    _check(lib("ecdsa").dt_ecdsa_sign_finish(SCALAR_CURVES.index(curve), *map(_bp, cols), int(flags), _bp(sig), _bp(recid), _bp(ok), n),
+           f"{curve} ecdsa sign_finish")
+    return sig, recid, ok
+
+
+def ecdsa_verify_check(curve, a_xy, a_inf, b_xy, b_inf, sig, ok_in):
+    """dt_ecdsa_verify_check over lists of byte strings (a_xy, b_xy: x || y; sig: r || s) and lists of flags -> ok (n,) uint8"""
+    nb = 48 if curve == "p384" else 32
+    n = len(sig)
+    assert len(a_xy) == len(a_inf) == len(b_xy) == len(b_inf) == len(ok_in) == n
+    ok = np.array(ok_in, dtype=np.uint8)
+    cols = [_byte_rows(a_xy, 2 * nb), np.array(a_inf, dtype=np.uint8), _byte_rows(b_xy, 2 * nb), np.array(b_inf, dtype=np.uint8), _byte_rows(sig, 2 * nb)]
+    _check(lib("ecdsa").dt_ecdsa_verify_check(SCALAR_CURVES.index(curve), *map(_bp, cols), _bp(ok), n), f"{curve} ecdsa verify_check")
+    return ok

@@ -130,9 +130,11 @@ def test_random_and_edge_cases_vs_oracle(ctx, cn):
 
 
 def test_x_coordinate_wraparound(ctx):
-    """r + n < p: signatures whose R.x lies in [n, p) must still verify (x mod n == r).  Such points cannot be
-    found by search (probability 2^-128 on these curves), so the check kernel's second candidate is exercised
-    through its algebra instead: a valid signature stays valid and r + n is never accepted as r itself."""
+    """r + n < p: a signature whose x(R) lies in [n, p) must still verify (x mod n == r).  No search finds such an R = k G (2^-128
+    on this curve), but one is constructed: lift the smallest on-curve x above n to R, choose s and z, set r = x - n and
+    Q = r^-1 (s R - z G).  It verifies by the check kernel's second candidate, its twin with r + 1 does not, and an ordinary signature
+    stays valid.  tests/test_gpu_ecdsa_wrap.py has the classes around this branch on all three curves."""
+    import ecdsa_wrap_vectors as W
     c = M.K256
     cv = ctx.curve("k256")
     d, k, z = 12345, 67890, hashlib.sha256(b"wrap").digest()
@@ -140,6 +142,13 @@ def test_x_coordinate_wraparound(ctx):
     Q = M.affine_mul(c, d, (c.gx, c.gy))
     tob = lambda v: v.to_bytes(32, "big")
     assert cv.ecdsa_verify(z, tob(r) + tob(s), tob(Q[0]) + tob(Q[1]))[0] == 1
+    R = M.decompress(c, W.anchors("k256").lo, 0)
+    r = R[0] - c.n
+    assert c.n < R[0] < c.p and 0 < r
+    Q = W.key_for(c, R, r, s, z)
+    assert M.ecdsa_verify_prehashed(c, Q, z, r, s, reject_high_s=True) and not M.ecdsa_verify_prehashed(c, Q, z, r + 1, s, reject_high_s=True)
+    got = cv.ecdsa_verify(z + z, tob(r) + tob(s) + tob(r + 1) + tob(s), 2 * (tob(Q[0]) + tob(Q[1])))
+    assert got.tolist() == [1, 0]
 
 
 def test_large_batch_all_valid_and_sparse_invalid(ctx):
@@ -285,7 +294,7 @@ def test_public_key_recovery(ctx, cn, ref_vectors):
         m = i % 8
         r = int.from_bytes(sigs[i][:nb], "big"); s = int.from_bytes(sigs[i][nb:], "big")
         if m == 0: rid[i] ^= 1
-        elif m == 1: rid[i] |= 2                    # r + n: almost always >= p or not on the curve
+        elif m == 1: rid[i] |= 2                    # r + n >= p for these random r (p - n < 2^191); tests/test_gpu_ecdsa_wrap.py has constructed r with r + n < p
         elif m == 2: s = c.n - s                    # high s: refused on k256, a different key elsewhere
         elif m == 3: r = 0
         elif m == 4: s = c.n
