@@ -30,8 +30,9 @@ static constexpr u32 C_LO = 977;   // C = 2^32 + C_LO
 // ECGPU_K256_BRANCHFREE before including this header - ops_k256_ct.hip: the kernels that run on SECRET scalars - gets them executed
 // unconditionally instead: each of these blocks is a no-op when its carry is zero (it ripples a zero and folds a zero), so running it
 // always gives the same values and leaves no branch that depends on data (VERDICT r3 missing 4; the reference's 5x52 lazy limbs need no
-// carry branch, k256/src/arithmetic/field/field_5x52.rs:252-285).  Cost: 5 + 3 carry instructions per multiplication, 6 + 2 per
-// addition / subtraction / small shift (measured on the constant-time kernels: profiles/r04_ab_measurements.txt).
+// carry branch, k256/src/arithmetic/field/field_5x52.rs:252-285).  Cost: 5 + 5 instructions per multiplication (the ripple, two selects
+// on the carry's lane mask and three carry instructions), 6 + 2 per addition / subtraction / small shift (measured on the
+// constant-time kernels with 5 + 3: profiles/r04_ab_measurements.txt).
 #ifdef ECGPU_K256_BRANCHFREE
 #define ECGPU_K256_RARE(cond) true
 #else
@@ -68,25 +69,98 @@ ECGPU_HD void fold_top(u32* r, u64 T) {
 // r += T * C for T < 2^40 (T*C is at most three words).  The carry out of word 2 is rare (~2^-26):
 // it takes a branch that ripples it and, if 2^256 is crossed, folds once more (the wrapped value is
 // then tiny, so that last fold cannot carry).
-ECGPU_HD void fold_top_fast(u32* r, u64 T) {
-  const u32 t0 = (u32)T, t1 = (u32)(T >> 32);
-  const u64 p = (u64)t0 * C_LO;                     // t0 * 977
-  const u32 s1 = (u32)(p >> 32) + t1 * C_LO;        // < 2^19
-  u32 ca = 0;
-  const u32 a1 = addc(s1, t0, ca);                  // + (T << 32)
-  const u32 a2 = t1 + ca;
-  u32 c = 0;
-  r[0] = addc(r[0], (u32)p, c);
-  r[1] = addc(r[1], a1, c);
-  r[2] = addc(r[2], a2, c);
-  if (ECGPU_K256_RARE(c != 0)) {
-#pragma unroll
-    for (int i = 3; i < 8; i++) r[i] = addc(r[i], 0u, c);
+//
+// T = t0 + t1 2^32 arrives as the two words the reduction's carry chains end in (add_high_chain below).
+// T * C = t0 * 977 + (T + t1 * 977) * 2^32, and both halves ride on a multiply's 64-bit addend:
+//   (r0, r1) += t0 * 977         one v_mad_u64_u32 whose addend is the pair (r0, r1); its carry k1 belongs to word 2
+//   M = T + t1 * 977             one v_mad_u64_u32 whose addend is T itself (SMALL, t1 <= 1 and then t0 + 977 < 2^32: the low word
+//                                is one v_mad_u32_u24 and the high word is t1); M < 2^41
+//   (r1, r2) += M + k1 * 2^32    three carry instructions: k1 joins M's high word first, so ONE carry comes out of word 2
+// Five instructions.  On the device the carries between the statements are lane masks in scalar-register pairs, and 977 comes from a
+// scalar register (the columns' fold products read theirs from a VGPR).
+namespace nc_bound {
+using u128 = unsigned __int128;
+static_assert(((u128)1 << 40) + 0xFFu * (u128)C_LO < ((u128)1 << 41), "M = T + t1 * 977 for T < 2^40: its high word + k1 cannot carry");
+static_assert(((u128)1 << 11) + 2 + C_LO < ((u128)1 << 32), "SMALL: t1 = 1 leaves t0 < 2^11 + 2, so t0 + 977 does not wrap");
+}  // namespace nc_bound
+template <bool SMALL>
+ECGPU_HD void fold_top_words(u32* r, u32 t0, u32 t1) {
+#if ECGPU_ASM
+  u64 r01 = ((u64)r[1] << 32) | r[0];
+  u64 k;                                        // the carry flag in flight: first the first mad's (k1), then word 2's
+  asm("v_mad_u64_u32 %0, %1, %2, %3, %0" : "+v"(r01), "=s"(k) : "v"(t0), "s"(C_LO));
+  u32 ml, mh;
+  if constexpr (SMALL) {
+    asm("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(ml) : "v"(t1), "s"(C_LO), "v"(t0));
+    mh = t1;
+  } else {
+    const u64 T = ((u64)t1 << 32) | t0;
+    u64 m;
+    asm("v_mad_u64_u32 %0, vcc, %1, %2, %3" : "=v"(m) : "v"(t1), "s"(C_LO), "v"(T) : "vcc");
+    ml = (u32)m; mh = (u32)(m >> 32);
+  }
+  r[0] = (u32)r01;
+  u32 r1 = (u32)(r01 >> 32);
+  asm("v_addc_co_u32 %[mh], %[k], 0, %[mh], %[k]\n\t"
+      "v_add_co_u32 %[r1], vcc, %[r1], %[ml]\n\t"
+      "v_addc_co_u32 %[r2], %[k], %[r2], %[mh], vcc"
+      : [r1] "+v"(r1), [r2] "+v"(r[2]), [mh] "+v"(mh), [k] "+s"(k)
+      : [ml] "v"(ml)
+      : "vcc");
+  r[1] = r1;
+  if (ECGPU_K256_RARE(k != 0)) {
+    // ripple the carry (a lane mask) through words 3..7; what comes out of word 7 crossed 2^256
+    asm("v_addc_co_u32 %0, %5, 0, %0, %5\n\t"
+        "v_addc_co_u32 %1, %5, 0, %1, %5\n\t"
+        "v_addc_co_u32 %2, %5, 0, %2, %5\n\t"
+        "v_addc_co_u32 %3, %5, 0, %3, %5\n\t"
+        "v_addc_co_u32 %4, %5, 0, %4, %5"
+        : "+v"(r[3]), "+v"(r[4]), "+v"(r[5]), "+v"(r[6]), "+v"(r[7]), "+s"(k));
+    u32 c, cc;                                  // the lanes that wrapped add C: 977 to word 0, 1 to word 1
+    asm("v_cndmask_b32 %0, 0, 1, %2\n\t"
+        "v_cndmask_b32 %1, 0, %3, %2"
+        : "=&v"(c), "=v"(cc) : "s"(k), "v"(C_LO));
     u32 c2 = 0;
-    r[0] = addc(r[0], c ? C_LO : 0u, c2);
+    r[0] = addc(r[0], cc, c2);
     r[1] = addc(r[1], c, c2);
     r[2] = addc(r[2], 0u, c2);
   }
+#else
+  const u64 a = (u64)t0 * C_LO + r[0];               // < 2^43: the sum with r1 * 2^32 may carry (k1)
+  const u64 r01 = a + ((u64)r[1] << 32);
+  const u32 k1 = r01 < a ? 1u : 0u;
+  const u64 m = (SMALL ? (u64)(t1 * C_LO + t0) | ((u64)t1 << 32) : (((u64)t1 << 32) | t0) + (u64)t1 * C_LO) + ((u64)k1 << 32);
+  u32 c = 0;
+  r[0] = (u32)r01;
+  r[1] = addc((u32)(r01 >> 32), (u32)m, c);
+  r[2] = addc(r[2], (u32)(m >> 32), c);
+  ECGPU_TAIL_NOTE("fold:k1", k1 != 0);
+  ECGPU_TAIL_NOTE("fold:ripple", c != 0);
+  if (ECGPU_K256_RARE(c != 0)) {
+#pragma unroll
+    for (int i = 3; i < 8; i++) r[i] = addc(r[i], 0u, c);
+    ECGPU_TAIL_NOTE("fold:second", c != 0);
+    u32 c2 = 0;
+    r[0] = addc(r[0], c * C_LO, c2);
+    r[1] = addc(r[1], c, c2);
+    r[2] = addc(r[2], 0u, c2);
+  }
+#endif
+}
+ECGPU_HD void fold_top_fast(u32* r, u64 T) { fold_top_words<false>(r, (u32)T, (u32)(T >> 32)); }
+// r = t + h * 2^32 on words 0..7 (r[0] = t[0], r[i] = t[i] + h[i-1]), and the same carry chain runs on through two more words:
+// t0 = xl + yl + carry, t1 = xh + yh + carry; the caller's bound says that t1 does not carry.  This is how every reduction assembles
+// its overflow count T = t0 + t1 2^32: v_addc_co_u32 adds two registers and a carry flag, so no flag is turned into a word and no
+// zero-extended 64-bit pair is built.
+ECGPU_HD void add_high_chain(u32* r, const u32* t, const u32* h, u32 xl, u32 yl, u32 xh, u32 yh, u32& t0, u32& t1) {
+  u32 cy = 0;
+  r[0] = t[0];
+#pragma unroll
+  for (int i = 1; i < 8; i++) r[i] = addc(t[i], h[i - 1], cy);
+  ECGPU_TAIL_NOTE("chain:word7", cy != 0);
+  t0 = addc(xl, yl, cy);
+  ECGPU_TAIL_NOTE("chain:t0", cy != 0);
+  t1 = addc(xh, yh, cy);
 }
 
 // r = a * b mod p (weakly reduced).  field_5x52.rs:288-449 (mul_inner) is the reference.
@@ -122,6 +196,35 @@ ECGPU_HD void mul_low_column(u32* t, Acc96& c, const u32* a, const u32* b, const
   mac_product_column<8, K, 1, true, 1>(c, a, b, xa, xb);      // h[K] * 977 first: < 2^43 with the carry-in (nc_bound)
   t[K] = acc_pop(c);
 }
+// The tail of the four products that fold on their columns (mul, mul_add2, mul_add_sqr and their exact forms): H * 2^32, the other
+// half of H * C, is one carry chain over words 1..7, and the same chain runs on into the overflow count T above 2^256:
+//   t0 = c.lo's low word + h[7] + carry,  t1 = c.lo's high word + h8 + carry          (add_high_chain)
+// c: what column 7 left, < 2^37.  h8 (WORD16): word 16 of a sum of two products, 0 or 1; 2^512 = C^2 mod p, so it adds C = 2^32 + 977
+// to T: its 2^32 is the h8 of t1, its 977 goes into c.lo first (a 24-bit multiply-add into h[7] or into c.lo's low word could wrap:
+// all-ones operands give h[7] = 2^32 - 1 with h8 = 1).  T < 2^38.
+namespace nc_bound {
+static_assert(((u128)1 << 37) + C_LO + 0xFFFFFFFFu + 1 + ((u128)1 << 32) < ((u128)1 << 38), "T = c.lo + h[7] + carry + h8 * C < 2^38: t1 does not carry");
+}  // namespace nc_bound
+template <bool WORD16>
+ECGPU_HD void mul_finish(FeK256& r, const u32* t, const u32* h, const Acc96& c, u32 h8) {
+  u32 t0, t1;
+  if constexpr (WORD16) {
+    u32 e;                                              // h8 * 977, one 24-bit multiply (not a select on h8 != 0)
+#if ECGPU_ASM
+    asm("v_mul_u32_u24 %0, %1, %2" : "=v"(e) : "v"(h8), "s"(C_LO));
+#else
+    e = h8 * C_LO;
+#endif
+    u32 k = 0;
+    const u32 cl0 = addc((u32)c.lo, e, k);
+    const u32 cl1 = addc((u32)(c.lo >> 32), 0u, k);
+    add_high_chain(r.v, t, h, cl0, h[7], cl1, h8, t0, t1);
+    ECGPU_TAIL_NOTE("mul:h8", h8 != 0);
+  } else {
+    add_high_chain(r.v, t, h, (u32)c.lo, h[7], (u32)(c.lo >> 32), 0u, t0, t1);
+  }
+  fold_top_words<false>(r.v, t0, t1);
+}
 ECGPU_HD void mul_exact(FeK256& r, const FeK256& a, const FeK256& b) {
   u32 h[8], t[8];
   Acc96 c{0, 0};
@@ -135,13 +238,7 @@ ECGPU_HD void mul_exact(FeK256& r, const FeK256& a, const FeK256& b) {
   mul_low_column<2>(t, c, a.v, b.v, h); mul_low_column<3>(t, c, a.v, b.v, h);
   mul_low_column<4>(t, c, a.v, b.v, h); mul_low_column<5>(t, c, a.v, b.v, h);
   mul_low_column<6>(t, c, a.v, b.v, h); mul_low_column<7>(t, c, a.v, b.v, h);
-  // H * 2^32 (the other half of H * C) is one carry chain; its top word joins the overflow above 2^256
-  u32 cy = 0;
-  r.v[0] = t[0];
-#pragma unroll
-  for (int i = 1; i < 8; i++) r.v[i] = addc(t[i], h[i - 1], cy);
-  const u64 T = c.lo + h[7] + cy;
-  fold_top_fast(r.v, T);
+  mul_finish<false>(r, t, h, c, 0);
 }
 
 // Speculative products (SPEC; ECGPU_K256_SPEC_PRODUCTS: the throughput build of the variable-base and signature kernels).  After its no-carry products a column starts
@@ -201,16 +298,6 @@ ECGPU_HD void mul_low_column_spec(u32* t, Acc96& c, const u32* a, const u32* b, 
   raised |= k;
   t[K] = acc_pop(c);
 }
-// the tail of the three products: H * 2^32 (the other half of H * C) is one carry chain; its top word joins the overflow above 2^256.
-// h8: word 16 of a sum of two products (0 or 1), handled as in mul_add2_exact.
-ECGPU_HD void mul_finish(FeK256& r, const u32* t, const u32* h, const Acc96& c, u32 h8) {
-  u32 cy = 0;
-  r.v[0] = t[0];
-#pragma unroll
-  for (int i = 1; i < 8; i++) r.v[i] = addc(t[i], h[i - 1], cy);
-  const u64 T = c.lo + h[7] + cy + (((u64)h8 << 32) | (h8 ? C_LO : 0u));     // < 2^38
-  fold_top_fast(r.v, T);
-}
 ECGPU_HD void mul(FeK256& r, const FeK256& a, const FeK256& b) {
   u32 h[8], t[8];
   u64 raised = 0;
@@ -225,7 +312,7 @@ ECGPU_HD void mul(FeK256& r, const FeK256& a, const FeK256& b) {
   mul_low_column_spec<2>(t, c, a.v, b.v, h, raised); mul_low_column_spec<3>(t, c, a.v, b.v, h, raised);
   mul_low_column_spec<4>(t, c, a.v, b.v, h, raised); mul_low_column_spec<5>(t, c, a.v, b.v, h, raised);
   mul_low_column_spec<6>(t, c, a.v, b.v, h, raised); mul_low_column_spec<7>(t, c, a.v, b.v, h, raised);
-  mul_finish(r, t, h, c, 0);
+  mul_finish<false>(r, t, h, c, 0);
 }
 #endif
 
@@ -261,12 +348,7 @@ ECGPU_HD void mul_add2_exact(FeK256& r, const FeK256& a, const FeK256& b, const 
   mul2_low_column<2>(t, c, a.v, b.v, e.v, f.v, h); mul2_low_column<3>(t, c, a.v, b.v, e.v, f.v, h);
   mul2_low_column<4>(t, c, a.v, b.v, e.v, f.v, h); mul2_low_column<5>(t, c, a.v, b.v, e.v, f.v, h);
   mul2_low_column<6>(t, c, a.v, b.v, e.v, f.v, h); mul2_low_column<7>(t, c, a.v, b.v, e.v, f.v, h);
-  u32 cy = 0;
-  r.v[0] = t[0];
-#pragma unroll
-  for (int i = 1; i < 8; i++) r.v[i] = addc(t[i], h[i - 1], cy);
-  const u64 T = c.lo + h[7] + cy + (((u64)h8 << 32) | (h8 ? C_LO : 0u));     // < 2^38
-  fold_top_fast(r.v, T);
+  mul_finish<true>(r, t, h, c, h8);
 }
 
 #if !ECGPU_K256_SPEC_PRODUCTS
@@ -308,7 +390,7 @@ ECGPU_HD void mul_add2(FeK256& r, const FeK256& a, const FeK256& b, const FeK256
   mul2_low_column_spec<2>(t, c, a.v, b.v, e.v, f.v, h, raised); mul2_low_column_spec<3>(t, c, a.v, b.v, e.v, f.v, h, raised);
   mul2_low_column_spec<4>(t, c, a.v, b.v, e.v, f.v, h, raised); mul2_low_column_spec<5>(t, c, a.v, b.v, e.v, f.v, h, raised);
   mul2_low_column_spec<6>(t, c, a.v, b.v, e.v, f.v, h, raised); mul2_low_column_spec<7>(t, c, a.v, b.v, e.v, f.v, h, raised);
-  mul_finish(r, t, h, c, h8);
+  mul_finish<true>(r, t, h, c, h8);
 }
 #endif
 
@@ -392,12 +474,7 @@ ECGPU_HD void mul_add_sqr_exact(FeK256& r, const FeK256& a, const FeK256& b, con
   mulsq_low_column<2>(t, c, a.v, b.v, s.v, e, d, h); mulsq_low_column<3>(t, c, a.v, b.v, s.v, e, d, h);
   mulsq_low_column<4>(t, c, a.v, b.v, s.v, e, d, h); mulsq_low_column<5>(t, c, a.v, b.v, s.v, e, d, h);
   mulsq_low_column<6>(t, c, a.v, b.v, s.v, e, d, h); mulsq_low_column<7>(t, c, a.v, b.v, s.v, e, d, h);
-  u32 cy = 0;
-  r.v[0] = t[0];
-#pragma unroll
-  for (int i = 1; i < 8; i++) r.v[i] = addc(t[i], h[i - 1], cy);
-  const u64 T = c.lo + h[7] + cy + (((u64)h8 << 32) | (h8 ? C_LO : 0u));     // < 2^38
-  fold_top_fast(r.v, T);
+  mul_finish<true>(r, t, h, c, h8);
 }
 
 #if !ECGPU_K256_SPEC_PRODUCTS
@@ -452,11 +529,16 @@ ECGPU_HD void mul_add_sqr(FeK256& r, const FeK256& a, const FeK256& b, const FeK
   mulsq_low_column_spec<2>(t, c, a.v, b.v, s.v, e, d, h, raised); mulsq_low_column_spec<3>(t, c, a.v, b.v, s.v, e, d, h, raised);
   mulsq_low_column_spec<4>(t, c, a.v, b.v, s.v, e, d, h, raised); mulsq_low_column_spec<5>(t, c, a.v, b.v, s.v, e, d, h, raised);
   mulsq_low_column_spec<6>(t, c, a.v, b.v, s.v, e, d, h, raised); mulsq_low_column_spec<7>(t, c, a.v, b.v, s.v, e, d, h, raised);
-  mul_finish(r, t, h, c, h8);
+  mul_finish<true>(r, t, h, c, h8);
 }
 #endif
 
-// reduce a 16-word integer modulo p: lo + hi * 977 + (hi << 32), then fold what spills over 2^256
+// reduce a 16-word integer modulo p: lo + hi * 977 + (hi << 32), then fold what spills over 2^256.  Two carry chains, lo + U and
+// + (hi << 32), and each runs one word further into the overflow count T: x = top + c1 (top = U's word 8, < 2^11: no carry), then
+// t0 = x + w[15] + c2 and t1 = the carry of that, 0 or 1 (add_high_chain).
+namespace nc_bound {
+static_assert((((u128)1 << 37) + (u128)0xFFFFFFFFu * C_LO) >> 32 < ((u128)1 << 11), "top = U >> 256 < 2^11: top + c1 does not carry, T < 2^32 + 2^11 + 2");
+}  // namespace nc_bound
 ECGPU_HD void reduce16(FeK256& r, const u32* w) {
   u32 u[8];
   u64 acc = 0;
@@ -465,15 +547,23 @@ ECGPU_HD void reduce16(FeK256& r, const u32* w) {
     acc = (u64)w[8 + k] * C_LO + (acc >> 32);
     u[k] = (u32)acc;
   }
-  u32 c1 = 0, c2 = 0;
+  u32 c1 = 0;
   u32 t[8];
 #pragma unroll
   for (int k = 0; k < 8; k++) t[k] = addc(w[k], u[k], c1);
-  r.v[0] = t[0];
-#pragma unroll
-  for (int k = 1; k < 8; k++) r.v[k] = addc(t[k], w[8 + k - 1], c2);
-  const u64 T = (acc >> 32) + c1 + c2 + w[15];
-  fold_top_fast(r.v, T);
+  ECGPU_TAIL_NOTE("sqr:c1", c1 != 0);
+  const u32 x = addc((u32)(acc >> 32), 0u, c1);
+  // t1 = 0 + 0 + carry stays on the chain (one v_addc_co_u32) when the compiler cannot see that the zero is one: a loop-invariant
+  // register, set once outside the loops
+#if ECGPU_ASM
+  u32 z;
+  asm("v_mov_b32 %0, 0" : "=v"(z));
+#else
+  const u32 z = 0;
+#endif
+  u32 t0, t1;
+  add_high_chain(r.v, t, w + 8, x, w[15], z, 0u, t0, t1);
+  fold_top_words<true>(r.v, t0, t1);
 }
 
 // r = a^2 mod p

@@ -48,6 +48,12 @@
 #ifndef ECGPU_SPEC_NOTE
 #define ECGPU_SPEC_NOTE(site, column, raised) ((void)0)
 #endif
+// Hook at the tail of every k256 reduction (fe_k256.hpp: the overflow word T on the carry chains, the fold of T * C, the rare ripple
+// behind it): empty in the product, and `cond` is NOT evaluated there.  The test-only host build counts, per site name, how often
+// `cond` holds, which is how the tests show that their operands reach both chain carries, word 16, the ripple and the second fold.
+#ifndef ECGPU_TAIL_NOTE
+#define ECGPU_TAIL_NOTE(site, cond) ((void)0)
+#endif
 
 namespace ecgpu {
 
